@@ -7,8 +7,10 @@ its OWN KV cache (61 x 338 MB = 20.6 GB resident in HBM, so nothing is re-served
 All inputs are resident in HBM before the timed region.  Multi-GPU = DP-attention (each rank owns its
 requests and pages, no data-path collective): weak scaling, value = total tokens/s over all ranks.
 
-Prints ONE JSON line (rank 0) with `roofline` (live HIP-event timing of the dominant kernel on its launch stream)
-and `cpu_baseline` (the oracle's restatement of the reference's torch-native CPU attention path, bounded sample).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`, `ms_per_step`);
+`--dump-outputs DIR` also writes what the last timed step returned.  `--full` adds every other measurement to the same line: `roofline`
+(live HIP-event timing of the dominant kernel on its launch stream), `gemm`, `variants`, `cpu_baseline` (the oracle's restatement of
+the reference's torch-native CPU attention path, bounded sample) and, at N > 1, the config-4 sub-record `cfg4`.
 """
 import argparse
 import json
@@ -198,6 +200,22 @@ def layer_call(fm, wl, l, meta, ns, fused=None):
     return fm.flash_mla_ckv_fp8_per_token(qn, qr, k_lora.view(pages, 64, 1, 512), k_rope.view(pages, 64, 1, 64), qs,
                                           k_scale.view(pages, 64, 1, 1), wl["block_table"], wl["seqlens"], 512, meta, ns,
                                           SCALE, True)
+
+
+DUMP_SAMPLE = 1 << 17   # elements of every layer's `o` that --dump-outputs keeps
+
+
+def dump_outputs(path, held):
+    """--dump-outputs: what the last timed step handed back, per layer (o bf16 [bs, s_q, H, 512], lse f32 [bs, H, s_q]), as float32 .npy:
+    `lse.npy` [layers, bs, H, s_q] whole; `o_sample.npy` [layers, DUMP_SAMPLE] = the same fixed, seeded sample of elements of every layer's
+    flattened o (all of o in float32 is 61 x 33.5 MB).  32 MB + 4 MB at the headline shape."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    o0 = held[0][0]
+    idx = torch.randint(0, o0.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(576)).to(o0.device)
+    np.save(os.path.join(path, "o_sample.npy"), torch.stack([o.reshape(-1)[idx].float() for o, _ in held]).cpu().numpy())
+    np.save(os.path.join(path, "lse.npy"), torch.stack([lse.float() for _, lse in held]).cpu().numpy())
 
 
 def k1_ragged_variant(dev, layers=61):
@@ -736,6 +754,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure roofline, gemm, variants, cpu_baseline and (N > 1) the config-4 sub-record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/o_sample.npy and DIR/lse.npy (float32): see dump_outputs")
     ap.add_argument("--layers", type=int, default=LAYERS, help=argparse.SUPPRESS)
     ap.add_argument("--no-cpu-baseline", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-graph", action="store_true", help=argparse.SUPPRESS)
@@ -780,9 +802,17 @@ def main():
     meta, ns = fm.get_mla_metadata(wl["seqlens"], S_Q * H, 1)
     torch.cuda.synchronize()
 
+    # (o, lse) of every layer of the latest step() call — of the captured step under a hipGraph, where each replay refills them.  Held only
+    # when they are to be written: a run without --dump-outputs frees each layer's outputs at once, as it always did
+    keep = a.dump_outputs is not None and rank == 0
+    held = []
+
     def step():
         # K3 once per decode step, as the reference's backend does in init_forward_metadata (flashmla_backend.py:307-321)
         m_step, ns_step = fm.get_mla_metadata(wl["seqlens"], S_Q * H, 1)
+        if keep:
+            held[:] = [layer_call(fm, wl, l, m_step, ns_step) for l in range(layers)]
+            return
         for l in range(layers):
             layer_call(fm, wl, l, m_step, ns_step)
 
@@ -822,12 +852,16 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / a.steps * 1e3
     tokens_per_s = world * BS / (ms_per_step * 1e-3) * (layers / LAYERS)   # (a step of fewer layers is scaled to the 61-layer step)
+    if keep:
+        dump_outputs(a.dump_outputs, held)
+        del held[:]
 
+    # ==== everything below the headline is measured under --full only: a plain run goes straight to its result line ====
     # ---- sub-records of the same step (rank 0, N = 1): (a) the optional fused quant launch (flash_mla_fp8.quantize_q_and_cache_k: an
     #      extension entry point an integrator may call instead of K5 + K4 — NOT what the unmodified FlashMLABackend calls, hence
     #      not the headline), (b) the quant launches alone, so that K1's share of the timed step can be read off ----
     step_variants = None
-    if rank == 0 and world == 1 and graph is not None:
+    if a.full and rank == 0 and world == 1 and graph is not None:
         def timed_graph(body, reps):
             s3 = torch.cuda.Stream()
             s3.wait_stream(torch.cuda.current_stream())
@@ -877,7 +911,7 @@ def main():
 
     # ---- roofline of the dominant kernel: K1 alone, HIP events on the launch stream (torch's current stream) ----
     roof = None
-    if rank == 0:
+    if a.full and rank == 0:
         pages = wl["pages"]
         qn, qs, qr = fm.quantize_ckv_per_token_head(wl["q"], 512)
 
@@ -960,7 +994,7 @@ def main():
     cpu = None
     gemm = None
     variants = None
-    if rank == 0 and world == 1 and not a.no_gemm:
+    if a.full and rank == 0 and world == 1 and not a.no_gemm:
         wl = None
         torch.cuda.empty_cache()
         variants = {"cfg2_ragged": k1_ragged_variant(dev)}
@@ -988,7 +1022,7 @@ def main():
             gemm["dense"] = dense_roofline(dev)
         except Exception as ex_:   # an add-on: never at the expense of the headline record
             gemm["dense"] = {"error": f"{type(ex_).__name__}: {ex_}"[:200]}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline()
     # ---- N > 1: BASELINE config 4 (attention-TP + EP MoE decoder layers, every collective of the path inside the captured step)
     #      as a sub-record of the SAME json line — what makes a multi-GPU record of this path more than N independent replicas.
@@ -1002,7 +1036,7 @@ def main():
             print(json.dumps(line), flush=True)
 
     want4 = os.environ.get("FLUENT_BENCH_CFG4", "1")   # "0": never; "force": also at N = 1 (exercises this code on a 1-GPU box)
-    if (world > 1 and want4 != "0") or want4 == "force":
+    if a.full and ((world > 1 and want4 != "0") or want4 == "force"):
         # Every rank runs `bench.py --mode cfg4` as a CHILD process with its own rendezvous port: a hang is ended by the timeout
         # (the exact child is killed), and a hard fault in the multi-GPU transports — a peer mapping or a collective that aborts
         # the process — ends the child only: the DP record measured above is printed either way.
