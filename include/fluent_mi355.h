@@ -42,7 +42,8 @@ typedef void* fl_stream_t;
  * 101: FlMlaDecodeArgs gained struct_bytes (FIRST field: every later field moved — a C caller built against 100 must be recompiled) and
  *      block_table_cols (last); fl_topk_gate added.
  * 102: additive — fl_fused_add_rmsnorm_offset (GemmaRMSNorm: the 1 added in fp32), fl_mla_set_merge_timeout (+ the in-kernel split merge
- *      reports a timeout through the next fl_mla_decode call); no struct changed. */
+ *      reports a timeout through the next fl_mla_decode call); no struct changed.
+ *      (still 102, additive: fl_mha_prefill_ragged_bf16 with its own FlPrefillArgs — struct_bytes first, checked — and fl_merge_state.) */
 #define FL_ABI_VERSION 102
 const char* fl_last_error(void);
 int fl_version(void);
@@ -422,6 +423,43 @@ int64_t fl_gemm_bf16_nt_splitk_workspace_bytes(int64_t M, int N, int K);
 int fl_gemm_bf16_nt_splitk(const void* A, const void* B, void* C, int64_t M, int N, int K, int64_t a_stride_m,
                            int64_t b_stride_n, int64_t c_stride_m, int out_is_f32, void* workspace, int64_t workspace_bytes,
                            fl_stream_t stream);
+
+/* ---- P1: ragged bf16 MHA prefill attention — flashinfer.BatchPrefillWithRaggedKVCacheWrapper.forward / forward_return_lse
+ * (srt/layers/attention/flashinfer_mla_backend.py:449; layers/attention/chunker.py:304) — and flashinfer.merge_state
+ * (srt/models/deepseek_v2.py:1037-1071).  Per request b (query rows qo_indptr[b] .. qo_indptr[b+1], keys kv_indptr[b] .. kv_indptr[b+1])
+ * and head: o = softmax(sm_scale * q k^T + mask) v with bf16 operands, fp32 accumulation, bf16 P.  causal: bottom-right aligned — row i
+ * of a request sees keys j <= i + (kv_len - qo_len).  lse (optional) is BASE 2: log2 sum_j 2^(sm_scale * log2(e) * q.k_j); the only
+ * consumer is fl_merge_state, which reads the same base.  A row without a visible key (kv_len == 0, or above the causal diagonal) gets
+ * o = 0, lse = -inf.  MHA only (one KV head per query head); head dims (192, 128) only.  Strides in ELEMENTS, last dimension contiguous,
+ * rows 16-byte aligned (pointers, and strides multiples of 8); indptr values are clamped to [0, num_*_tokens].  Rows of `out` that
+ * belong to no request are not written. ---- */
+typedef struct FlPrefillArgs {
+  int32_t struct_bytes;      /* = sizeof(FlPrefillArgs) as the CALLER compiled it; anything else is refused */
+  int32_t batch;             /* B: requests */
+  int64_t num_q_tokens;      /* Tq: rows of q / out / lse */
+  int64_t num_kv_tokens;     /* Tk: rows of k / v */
+  int32_t num_heads;         /* H (query heads = KV heads) */
+  int32_t head_dim_qk, head_dim_vo;   /* 192, 128 */
+  int32_t causal;
+  float sm_scale;
+  int32_t reserved;          /* 0 */
+  const void* q;             /* bf16 [Tq, H, head_dim_qk] */
+  int64_t q_stride_token, q_stride_head;
+  const void* k;             /* bf16 [Tk, H, head_dim_qk] */
+  int64_t k_stride_token, k_stride_head;
+  const void* v;             /* bf16 [Tk, H, head_dim_vo] */
+  int64_t v_stride_token, v_stride_head;
+  const int32_t* qo_indptr;  /* i32 [B + 1], DEVICE */
+  const int32_t* kv_indptr;  /* i32 [B + 1], DEVICE */
+  void* out;                 /* bf16 [Tq, H, head_dim_vo] contiguous */
+  float* lse;                /* f32 [Tq, H] contiguous, base 2; NULL = not wanted */
+} FlPrefillArgs;
+int fl_mha_prefill_ragged_bf16(const FlPrefillArgs* args, fl_stream_t stream);
+/* Two attention states over disjoint key sets -> the state over their union: v_* bf16 [rows, head_dim] contiguous (rows = tokens x heads,
+ * head_dim % 8 == 0), s_* f32 [rows] base-2 lse.  m = max(s_a, s_b): v = (v_a 2^(s_a-m) + v_b 2^(s_b-m)) / (2^(s_a-m) + 2^(s_b-m)),
+ * s = m + log2(2^(s_a-m) + 2^(s_b-m)), in fp32.  A side with s = -inf returns the other side unchanged; both -inf: v = 0, s = -inf. */
+int fl_merge_state(const void* v_a, const float* s_a, const void* v_b, const float* s_b, void* v_out, float* s_out, int64_t rows,
+                   int head_dim, fl_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,9 +4,10 @@ silu_and_mul, activation.silu_and_mul_fuse_block_quant, comm.trtllm_{allreduce,r
 moe_fused_gate (the router selection feeding the EP dispatch, srt/layers/moe/topk.py:33,715) and
 apply_rope_with_cos_sin_cache_inplace (q_pe / k_pe rotation before K5/K4, srt/layers/rotary_embedding.py:31,203), plus the
 rmsnorm / fused_add_rmsnorm / norm._rmsnorm_fused_parallel (layernorm.py:26-31,293), topk_softmax / routing_flash (topk.py:33,845), the
-two attention-wrapper classes FlashMLABackend's base class constructs (flashinfer_mla_backend.py:124-142) as INERT objects
-(attention_wrappers.py) and `comm.vllm_ar` (C4).  Sampling / norm / prefill attention are out of scope (not named by the
-north star)."""
+two attention-wrapper classes FlashMLABackend's base class constructs (flashinfer_mla_backend.py:124-142; attention_wrappers.py):
+BatchMLAPagedAttentionWrapper as an INERT object, BatchPrefillWithRaggedKVCacheWrapper LIVE — the ragged bf16 MHA prefill (192/128)
+of the prompt path, with `merge_state` for its chunked-prefix form (csrc/mha_prefill_bf16.hip; lse in base 2) — and `comm.vllm_ar`
+(C4).  Sampling is out of scope (not named by the north star)."""
 from fluent_mi355.gemm import sgl_per_token_group_quant_fp8, silu_and_mul  # noqa: F401
 from fluent_mi355.router import moe_fused_gate, routing_flash, topk_softmax  # noqa: F401
 from fluent_mi355.rope import FusedSetKVBufferArg, apply_rope_with_cos_sin_cache_inplace  # noqa: F401
@@ -32,6 +33,8 @@ def dsv3_fused_a_gemm(hidden_states, weight_t):
 
 
 def merge_state(v_a, s_a, v_b, s_b):
-    """models/deepseek_v2.py:43 imports this name for the chunked-PREFILL attention merge (out of the decode hot path,
-    SURVEY §8 'out of scope').  Importable; calling it is refused."""
-    raise RuntimeError("flashinfer.merge_state: prefill attention state merge is outside the MI355X hot-path build")
+    """models/deepseek_v2.py:43,1037-1071: the chunked-prefill attention merge — two states (v [T, H, D] bf16, s [T, H] f32 lse in
+    BASE 2, as `forward_return_lse` returns it) over disjoint key sets -> (v, s) over their union (csrc/mha_prefill_bf16.hip)."""
+    from fluent_mi355.prefill import merge_state as _merge
+
+    return _merge(v_a, s_a, v_b, s_b)

@@ -3,9 +3,10 @@
 `flashinfer.BatchPrefillWithRaggedKVCacheWrapper(workspace, "NHD")` and three `flashinfer.BatchMLAPagedAttentionWrapper(
 workspace, backend="auto")`, and its indices updaters call `.plan(...)` / `.begin_forward(...)` on them
 (:344, :622-650).  On the FP8 MLA decode / verify path every attention call goes to `flash_mla_fp8` / `flash_mla_swap`
-instead (flashmla_backend.py:105-256), so these wrappers are INERT here: they hold the workspace, record the last plan, and
-refuse to run — a prefill through them is a different attention family (out of scope) and must fail loudly,
-not silently fall back."""
+instead (flashmla_backend.py:105-256), so `BatchMLAPagedAttentionWrapper` is INERT here: it holds the workspace, records the last
+plan, and refuses to run — loudly, not by a silent fall-back.  `BatchPrefillWithRaggedKVCacheWrapper` is LIVE: the ragged bf16 MHA
+prefill of the prompt path (forward_normal_extend :449, the chunked-prefix path layers/attention/chunker.py:281-312) runs on
+csrc/mha_prefill_bf16.hip through fluent_mi355/prefill.py; what that kernel does not serve raises RuntimeError."""
 from __future__ import annotations
 
 
@@ -33,8 +34,8 @@ class _InertWrapper:
 
     def run(self, *args, **kwargs):
         raise RuntimeError(f"{self._what}.run: not on the FP8 MLA decode / grouped-GEMM hot path this library replaces "
-                           "(flashmla_backend.py routes decode and verify to flash_mla_fp8 / flash_mla_swap); prefill through "
-                           "flashinfer has no MI355X implementation here")
+                           "(flashmla_backend.py routes decode and verify to flash_mla_fp8 / flash_mla_swap); paged MLA "
+                           "attention through flashinfer has no MI355X implementation here")
 
     forward = run
     forward_return_lse = run
@@ -43,12 +44,70 @@ class _InertWrapper:
 
 class BatchPrefillWithRaggedKVCacheWrapper(_InertWrapper):
     """flashinfer.BatchPrefillWithRaggedKVCacheWrapper(workspace, kv_layout) — flashinfer_mla_backend.py:124-126, used by
-    forward_extend's ragged prefill (:449)."""
+    forward_extend's ragged prefill (:449) and the prefix chunker (chunker.py:268-312).  `plan` / `begin_forward` only RECORD
+    (no device access, never raise); `run` / `forward` return o [Tq, H, 128] bf16, `run_return_lse` / `forward_return_lse`
+    (o, lse) with lse [Tq, H] f32 in BASE 2 (log2 of the sum of 2^(sm_scale * log2(e) * q.k)), the base `flashinfer.merge_state`
+    reads.  Served: bf16, MHA, head dims 192 / 128, NHD, causal (bottom-right aligned) or not; per-call `causal`, `sm_scale`,
+    `logits_soft_cap` override the plan's, `sm_scale=None` = head_dim_qk ** -0.5.  Everything else raises RuntimeError."""
     _what = "BatchPrefillWithRaggedKVCacheWrapper"
 
     def __init__(self, float_workspace_buffer=None, kv_layout: str = "NHD", *args, **kwargs):
         super().__init__(float_workspace_buffer, *args, **kwargs)
         self._kv_layout = kv_layout
+        self._plan = None
+
+    def plan(self, qo_indptr=None, kv_indptr=None, num_qo_heads=None, num_kv_heads=None, head_dim_qk=None, head_dim_vo=None,
+             *args, **kwargs):
+        self.last_plan = ((qo_indptr, kv_indptr, num_qo_heads, num_kv_heads, head_dim_qk, head_dim_vo) + args, kwargs)
+        self._plan = dict(kwargs, qo_indptr=qo_indptr, kv_indptr=kv_indptr, num_qo_heads=num_qo_heads, num_kv_heads=num_kv_heads,
+                          head_dim_qk=head_dim_qk, head_dim_vo=head_dim_qk if head_dim_vo is None else head_dim_vo, extra_args=args)
+
+    begin_forward = plan
+
+    def end_forward(self):
+        self.last_plan = self._plan = None
+
+    def _run(self, q, k, v, return_lse, causal=None, sm_scale=None, logits_soft_cap=None, **kwargs):
+        from fluent_mi355 import prefill
+
+        what, pl = self._what, self._plan
+        if pl is None:
+            raise RuntimeError(f"{what}.run before plan / begin_forward")
+        if self._kv_layout != "NHD":
+            raise RuntimeError(f"{what}: kv_layout {self._kv_layout!r}; only NHD is served")
+        causal = pl.get("causal", False) if causal is None else causal
+        sm_scale = pl.get("sm_scale") if sm_scale is None else sm_scale
+        cap = pl.get("logits_soft_cap") if logits_soft_cap is None else logits_soft_cap
+        if cap is not None and cap > 0:
+            raise RuntimeError(f"{what}: logits_soft_cap={cap} is not served by the MI355X prefill kernel")
+        if pl["extra_args"] or pl.get("custom_mask") is not None or pl.get("packed_custom_mask") is not None:
+            raise RuntimeError(f"{what}: custom masks are not served")
+        # every other option of flashinfer's plan / run must sit at its neutral value: nothing is silently ignored
+        neutral = {"pos_encoding_mode": "NONE", "window_left": -1, "use_fp16_qk_reduction": False, "rope_scale": None, "rope_theta": None,
+                   "k_scale": None, "v_scale": None, "out": None, "lse": None}
+        given = [(n, pl[n]) for n in neutral if n in pl] + [(n, x) for n, x in kwargs.items() if n != "enable_pdl"]
+        for name, val in given:
+            if name not in neutral or ((val is not None) if neutral[name] is None else (val != neutral[name])):
+                raise RuntimeError(f"{what}: {name}={val!r} is not served")
+        if pl["num_kv_heads"] != pl["num_qo_heads"]:
+            raise RuntimeError(f"{what}: MHA only (num_qo_heads={pl['num_qo_heads']}, num_kv_heads={pl['num_kv_heads']})")
+        if (pl["head_dim_qk"], pl["head_dim_vo"]) != (prefill.HEAD_DIM_QK, prefill.HEAD_DIM_VO):
+            raise RuntimeError(f"{what}: head dims {pl['head_dim_qk']}/{pl['head_dim_vo']}; only 192/128 are served")
+        return prefill.mha_prefill_ragged(q, k, v, pl["qo_indptr"], pl["kv_indptr"], bool(causal), sm_scale, return_lse)
+
+    def run(self, q=None, k=None, v=None, *args, return_lse: bool = False, **kwargs):
+        if args:
+            raise RuntimeError(f"{self._what}.run: unexpected positional arguments")
+        return self._run(q, k, v, return_lse, **kwargs)
+
+    def run_return_lse(self, q=None, k=None, v=None, **kwargs):
+        return self._run(q, k, v, True, **kwargs)
+
+    def forward(self, q=None, k=None, v=None, causal=None, **kwargs):
+        return self._run(q, k, v, False, causal=causal, **kwargs)
+
+    def forward_return_lse(self, q=None, k=None, v=None, causal=None, **kwargs):
+        return self._run(q, k, v, True, causal=causal, **kwargs)
 
 
 class BatchMLAPagedAttentionWrapper(_InertWrapper):

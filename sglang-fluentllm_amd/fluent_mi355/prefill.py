@@ -1,0 +1,105 @@
+"""P1: ragged bf16 MHA prefill attention and the attention-state merge (csrc/mha_prefill_bf16.hip) — what
+`flashinfer.BatchPrefillWithRaggedKVCacheWrapper.forward / forward_return_lse` (srt/layers/attention/flashinfer_mla_backend.py:449,
+layers/attention/chunker.py:304) and `flashinfer.merge_state` (models/deepseek_v2.py:1037-1071) run on the DeepSeek-V3 / LongCat MLA
+prompt path.  This module validates, fills the C struct and launches; nothing in it computes, copies or synchronises, and the only
+allocations are the outputs.  Anything the kernel does not serve raises RuntimeError — there is no library fallback.
+
+The log-sum-exp both functions speak is BASE 2: lse = log2 sum_j 2^(sm_scale * log2(e) * q.k_j) (flashinfer's convention)."""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from ._lib import check, lib, stream_ptr
+
+_vp, _i64, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+
+
+class FlPrefillArgs(ctypes.Structure):
+    """Mirror of `struct FlPrefillArgs` in include/fluent_mi355.h (field order is ABI)."""
+
+    _fields_ = [
+        ("struct_bytes", _i32), ("batch", _i32), ("num_q_tokens", _i64), ("num_kv_tokens", _i64), ("num_heads", _i32),
+        ("head_dim_qk", _i32), ("head_dim_vo", _i32), ("causal", _i32), ("sm_scale", ctypes.c_float), ("reserved", _i32),
+        ("q", _vp), ("q_stride_token", _i64), ("q_stride_head", _i64),
+        ("k", _vp), ("k_stride_token", _i64), ("k_stride_head", _i64),
+        ("v", _vp), ("v_stride_token", _i64), ("v_stride_head", _i64),
+        ("qo_indptr", _vp), ("kv_indptr", _vp), ("out", _vp), ("lse", _vp),
+    ]
+
+
+lib.fl_mha_prefill_ragged_bf16.argtypes = [ctypes.POINTER(FlPrefillArgs), _vp]
+lib.fl_mha_prefill_ragged_bf16.restype = ctypes.c_int
+lib.fl_merge_state.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, _vp]
+lib.fl_merge_state.restype = ctypes.c_int
+
+HEAD_DIM_QK, HEAD_DIM_VO = 192, 128
+
+
+def _operand(name, t, head_dim):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"mha_prefill_ragged: {name} must be a CUDA/HIP tensor")
+    if t.dtype != torch.bfloat16:
+        raise RuntimeError(f"mha_prefill_ragged: {name} is {t.dtype}; only bfloat16 is served")
+    if t.dim() != 3 or t.shape[2] != head_dim:
+        raise RuntimeError(f"mha_prefill_ragged: {name} must be [tokens, heads, {head_dim}] (head dims other than "
+                           f"{HEAD_DIM_QK}/{HEAD_DIM_VO} are not served), got {tuple(t.shape)}")
+    if t.numel() and (t.stride(2) != 1 or t.stride(0) % 8 or t.stride(1) % 8 or t.data_ptr() % 16):
+        raise RuntimeError(f"mha_prefill_ragged: {name} needs a contiguous last dimension and 16-byte aligned rows, strides {t.stride()}")
+
+
+def _indptr(name, t, device):
+    if not torch.is_tensor(t) or t.device != device or t.dtype != torch.int32 or t.dim() != 1 or t.numel() < 1 or not t.is_contiguous():
+        raise RuntimeError(f"mha_prefill_ragged: {name} must be a contiguous int32 [batch + 1] tensor on {device}")
+
+
+def mha_prefill_ragged(q, k, v, qo_indptr, kv_indptr, causal: bool, sm_scale: float | None = None, return_lse: bool = False):
+    """q [Tq, H, 192], k [Tk, H, 192], v [Tk, H, 128] bf16 (any token / head strides with 16-byte aligned rows; nothing is copied),
+    qo_indptr / kv_indptr int32 [B + 1] on the same device.  Returns o [Tq, H, 128] bf16, and with `return_lse` also the BASE-2
+    lse [Tq, H] f32.  `causal` is bottom-right aligned (row i of a request sees keys j <= i + kv_len - qo_len); a row that sees no key
+    gets o = 0, lse = -inf.  Rows of q that belong to no request are left unwritten."""
+    _operand("q", q, HEAD_DIM_QK)
+    _operand("k", k, HEAD_DIM_QK)
+    _operand("v", v, HEAD_DIM_VO)
+    H = q.shape[1]
+    if k.shape[1] != H or v.shape[1] != H:
+        raise RuntimeError(f"mha_prefill_ragged: MHA only — q has {H} heads, k {k.shape[1]}, v {v.shape[1]}")
+    if k.shape[0] != v.shape[0] or k.device != q.device or v.device != q.device:
+        raise RuntimeError("mha_prefill_ragged: k and v must have the same tokens and sit on q's device")
+    _indptr("qo_indptr", qo_indptr, q.device)
+    _indptr("kv_indptr", kv_indptr, q.device)
+    if kv_indptr.numel() != qo_indptr.numel():
+        raise RuntimeError("mha_prefill_ragged: qo_indptr and kv_indptr differ in length")
+    o = torch.empty(q.shape[0], H, HEAD_DIM_VO, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(q.shape[0], H, dtype=torch.float32, device=q.device) if return_lse else None
+    a = FlPrefillArgs()
+    a.struct_bytes = ctypes.sizeof(FlPrefillArgs)
+    a.batch, a.num_q_tokens, a.num_kv_tokens, a.num_heads = qo_indptr.numel() - 1, q.shape[0], k.shape[0], H
+    a.head_dim_qk, a.head_dim_vo, a.causal = HEAD_DIM_QK, HEAD_DIM_VO, int(bool(causal))
+    a.sm_scale = float(HEAD_DIM_QK ** -0.5 if sm_scale is None else sm_scale)
+    a.q, a.q_stride_token, a.q_stride_head = q.data_ptr(), q.stride(0), q.stride(1)
+    a.k, a.k_stride_token, a.k_stride_head = k.data_ptr(), k.stride(0), k.stride(1)
+    a.v, a.v_stride_token, a.v_stride_head = v.data_ptr(), v.stride(0), v.stride(1)
+    a.qo_indptr, a.kv_indptr, a.out = qo_indptr.data_ptr(), kv_indptr.data_ptr(), o.data_ptr()
+    a.lse = lse.data_ptr() if return_lse else None
+    check(lib.fl_mha_prefill_ragged_bf16(ctypes.byref(a), stream_ptr(q.device)), "fl_mha_prefill_ragged_bf16")
+    return (o, lse) if return_lse else o
+
+
+def merge_state(v_a, s_a, v_b, s_b):
+    """Attention states (v [T, H, D] bf16, s [T, H] f32 base-2 lse) over two disjoint key sets -> the state over their union.  A side
+    whose s is -inf returns the other side unchanged; both -inf: v = 0, s = -inf."""
+    for n, v, s in (("a", v_a, s_a), ("b", v_b, s_b)):
+        if not (torch.is_tensor(v) and torch.is_tensor(s) and v.is_cuda and s.device == v.device):
+            raise RuntimeError(f"merge_state: v_{n} / s_{n} must be CUDA/HIP tensors on one device")
+        if v.dtype != torch.bfloat16 or s.dtype != torch.float32 or v.dim() != 3 or s.shape != v.shape[:2]:
+            raise RuntimeError(f"merge_state: v_{n} bf16 [T, H, D] with s_{n} f32 [T, H], got {v.dtype} {tuple(v.shape)} / {s.dtype} {tuple(s.shape)}")
+        if not (v.is_contiguous() and s.is_contiguous()):
+            raise RuntimeError(f"merge_state: v_{n} / s_{n} must be contiguous")
+    if v_a.shape != v_b.shape or v_b.device != v_a.device or v_a.shape[2] % 8:
+        raise RuntimeError(f"merge_state: the two states differ in shape or device, or D is no multiple of 8: {tuple(v_a.shape)} / {tuple(v_b.shape)}")
+    v, s = torch.empty_like(v_a), torch.empty_like(s_a)
+    check(lib.fl_merge_state(v_a.data_ptr(), s_a.data_ptr(), v_b.data_ptr(), s_b.data_ptr(), v.data_ptr(), s.data_ptr(),
+                             s_a.numel(), v_a.shape[2], stream_ptr(v_a.device)), "fl_merge_state")
+    return v, s
