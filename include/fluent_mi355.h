@@ -43,7 +43,8 @@ typedef void* fl_stream_t;
  *      block_table_cols (last); fl_topk_gate added.
  * 102: additive — fl_fused_add_rmsnorm_offset (GemmaRMSNorm: the 1 added in fp32), fl_mla_set_merge_timeout (+ the in-kernel split merge
  *      reports a timeout through the next fl_mla_decode call); no struct changed.
- *      (still 102, additive: fl_mha_prefill_ragged_bf16 with its own FlPrefillArgs — struct_bytes first, checked — and fl_merge_state.) */
+ *      (still 102, additive: fl_mha_prefill_ragged_bf16 with its own FlPrefillArgs — struct_bytes first, checked — and fl_merge_state;
+ *      fl_mla_prefill_paged_bf16 with its own FlMlaPrefillArgs, struct_bytes first, checked.) */
 #define FL_ABI_VERSION 102
 const char* fl_last_error(void);
 int fl_version(void);
@@ -460,6 +461,43 @@ int fl_mha_prefill_ragged_bf16(const FlPrefillArgs* args, fl_stream_t stream);
  * s = m + log2(2^(s_a-m) + 2^(s_b-m)), in fp32.  A side with s = -inf returns the other side unchanged; both -inf: v = 0, s = -inf. */
 int fl_merge_state(const void* v_a, const float* s_a, const void* v_b, const float* s_b, void* v_out, float* s_out, int64_t rows,
                    int head_dim, fl_stream_t stream);
+
+/* ---- P2: absorbed (MQA) paged MLA attention over token-indexed KV — flashinfer.BatchMLAPagedAttentionWrapper.run with page size 1
+ * (srt/layers/attention/flashinfer_mla_backend.py:486-541 forward_absorbed, :472-483 decode / verify of the plain backend).  Per request b
+ * (query tokens qo_indptr[b] .. qo_indptr[b+1]; key j lives in slot kv_indices[kv_indptr[b] + j], j < kv_len = max(0, min(kv_len_arr[b],
+ * kv_indptr[b+1] - kv_indptr[b]))), token i and head h:  s = sm_scale (q_nope . ckv[slot, :512] + q_pe . kpe[slot, :64]),
+ * o = softmax(s + mask) ckv[slot, :512], with bf16 operands, fp32 accumulation, bf16 P.  causal: bottom-right aligned — token i sees keys
+ * j <= i + (kv_len - q_len).  lse (optional) is BASE 2, as fl_mha_prefill_ragged_bf16 / fl_merge_state speak it.  A row without a visible
+ * key gets o = 0, lse = -inf; rows of `out` that belong to no request are not written.  Head dims (512, 64) only.  Strides in ELEMENTS,
+ * last dimension contiguous, rows 16-byte aligned (pointers, and strides multiples of 8); qo_indptr values are clamped to [0, num_q_tokens],
+ * kv_indptr values to [0, num_kv_indices], slot indices to [0, num_kv_slots).  No split over the KV. ---- */
+typedef struct FlMlaPrefillArgs {
+  int32_t struct_bytes;      /* = sizeof(FlMlaPrefillArgs) as the CALLER compiled it; anything else is refused */
+  int32_t batch;             /* B: requests */
+  int64_t num_q_tokens;      /* T: rows of q_nope / q_pe / out / lse */
+  int64_t num_kv_slots;      /* N: rows of ckv / kpe */
+  int64_t num_kv_indices;    /* entries of kv_indices */
+  int32_t num_heads;         /* H */
+  int32_t head_dim_ckv, head_dim_kpe;   /* 512, 64 */
+  int32_t causal;
+  float sm_scale;
+  int32_t reserved;          /* 0 */
+  const void* q_nope;        /* bf16 [T, H, 512] */
+  int64_t q_nope_stride_token, q_nope_stride_head;
+  const void* q_pe;          /* bf16 [T, H, 64] */
+  int64_t q_pe_stride_token, q_pe_stride_head;
+  const void* ckv;           /* bf16 [N, 512] */
+  int64_t ckv_stride_slot;
+  const void* kpe;           /* bf16 [N, 64] */
+  int64_t kpe_stride_slot;
+  const int32_t* qo_indptr;  /* i32 [B + 1], DEVICE */
+  const int32_t* kv_indptr;  /* i32 [B + 1], DEVICE */
+  const int32_t* kv_indices; /* i32 [num_kv_indices], DEVICE */
+  const int32_t* kv_len_arr; /* i32 [B], DEVICE */
+  void* out;                 /* bf16 [T, H, 512] contiguous */
+  float* lse;                /* f32 [T, H] contiguous, base 2; NULL = not wanted */
+} FlMlaPrefillArgs;
+int fl_mla_prefill_paged_bf16(const FlMlaPrefillArgs* args, fl_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -5,9 +5,9 @@ moe_fused_gate (the router selection feeding the EP dispatch, srt/layers/moe/top
 apply_rope_with_cos_sin_cache_inplace (q_pe / k_pe rotation before K5/K4, srt/layers/rotary_embedding.py:31,203), plus the
 rmsnorm / fused_add_rmsnorm / norm._rmsnorm_fused_parallel (layernorm.py:26-31,293), topk_softmax / routing_flash (topk.py:33,845), the
 two attention-wrapper classes FlashMLABackend's base class constructs (flashinfer_mla_backend.py:124-142; attention_wrappers.py):
-BatchMLAPagedAttentionWrapper as an INERT object, BatchPrefillWithRaggedKVCacheWrapper LIVE — the ragged bf16 MHA prefill (192/128)
-of the prompt path, with `merge_state` for its chunked-prefix form (csrc/mha_prefill_bf16.hip; lse in base 2) — and `comm.vllm_ar`
-(C4).  Sampling is out of scope (not named by the north star)."""
+both LIVE: BatchPrefillWithRaggedKVCacheWrapper — the ragged bf16 MHA prefill (192/128) of the prompt path, with `merge_state` for
+its chunked-prefix form (csrc/mha_prefill_bf16.hip; lse in base 2) — and BatchMLAPagedAttentionWrapper — absorbed paged MLA attention
+(576/512, bf16, page size 1, ragged and causal; csrc/mla_prefill_bf16.hip) — and `comm.vllm_ar` (C4).  Sampling is out of scope (not named by the north star)."""
 from fluent_mi355.gemm import sgl_per_token_group_quant_fp8, silu_and_mul  # noqa: F401
 from fluent_mi355.router import moe_fused_gate, routing_flash, topk_softmax  # noqa: F401
 from fluent_mi355.rope import FusedSetKVBufferArg, apply_rope_with_cos_sin_cache_inplace  # noqa: F401

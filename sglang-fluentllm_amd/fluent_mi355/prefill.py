@@ -1,10 +1,11 @@
-"""P1: ragged bf16 MHA prefill attention and the attention-state merge (csrc/mha_prefill_bf16.hip) — what
+"""P1 / P2: ragged bf16 MHA prefill attention and the attention-state merge (csrc/mha_prefill_bf16.hip) — what
 `flashinfer.BatchPrefillWithRaggedKVCacheWrapper.forward / forward_return_lse` (srt/layers/attention/flashinfer_mla_backend.py:449,
 layers/attention/chunker.py:304) and `flashinfer.merge_state` (models/deepseek_v2.py:1037-1071) run on the DeepSeek-V3 / LongCat MLA
-prompt path.  This module validates, fills the C struct and launches; nothing in it computes, copies or synchronises, and the only
+prompt path — and absorbed paged MLA attention over token-indexed KV (csrc/mla_prefill_bf16.hip), what
+`flashinfer.BatchMLAPagedAttentionWrapper.run` (flashinfer_mla_backend.py:472-541) runs with page size 1.  This module validates, fills the C struct and launches; nothing in it computes, copies or synchronises, and the only
 allocations are the outputs.  Anything the kernel does not serve raises RuntimeError — there is no library fallback.
 
-The log-sum-exp both functions speak is BASE 2: lse = log2 sum_j 2^(sm_scale * log2(e) * q.k_j) (flashinfer's convention)."""
+The log-sum-exp all three functions speak is BASE 2: lse = log2 sum_j 2^(sm_scale * log2(e) * q.k_j) (flashinfer's convention)."""
 from __future__ import annotations
 
 import ctypes
@@ -103,3 +104,93 @@ def merge_state(v_a, s_a, v_b, s_b):
     check(lib.fl_merge_state(v_a.data_ptr(), s_a.data_ptr(), v_b.data_ptr(), s_b.data_ptr(), v.data_ptr(), s.data_ptr(),
                              s_a.numel(), v_a.shape[2], stream_ptr(v_a.device)), "fl_merge_state")
     return v, s
+
+
+class FlMlaPrefillArgs(ctypes.Structure):
+    """Mirror of `struct FlMlaPrefillArgs` in include/fluent_mi355.h (field order is ABI)."""
+
+    _fields_ = [
+        ("struct_bytes", _i32), ("batch", _i32), ("num_q_tokens", _i64), ("num_kv_slots", _i64), ("num_kv_indices", _i64),
+        ("num_heads", _i32), ("head_dim_ckv", _i32), ("head_dim_kpe", _i32), ("causal", _i32), ("sm_scale", ctypes.c_float),
+        ("reserved", _i32),
+        ("q_nope", _vp), ("q_nope_stride_token", _i64), ("q_nope_stride_head", _i64),
+        ("q_pe", _vp), ("q_pe_stride_token", _i64), ("q_pe_stride_head", _i64),
+        ("ckv", _vp), ("ckv_stride_slot", _i64), ("kpe", _vp), ("kpe_stride_slot", _i64),
+        ("qo_indptr", _vp), ("kv_indptr", _vp), ("kv_indices", _vp), ("kv_len_arr", _vp), ("out", _vp), ("lse", _vp),
+    ]
+
+
+lib.fl_mla_prefill_paged_bf16.argtypes = [ctypes.POINTER(FlMlaPrefillArgs), _vp]
+lib.fl_mla_prefill_paged_bf16.restype = ctypes.c_int
+
+HEAD_DIM_CKV, HEAD_DIM_KPE = 512, 64
+
+
+def _mla_rows(name, t, shape, what):
+    """bf16 CUDA/HIP tensor of `shape` (None = any size) with a contiguous last dimension and 16-byte aligned rows"""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"mla_prefill_paged: {name} must be a CUDA/HIP tensor")
+    if t.dtype != torch.bfloat16:
+        raise RuntimeError(f"mla_prefill_paged: {name} is {t.dtype}; only bfloat16 is served")
+    if t.dim() != len(shape) or any(w is not None and d != w for d, w in zip(t.shape, shape)):
+        raise RuntimeError(f"mla_prefill_paged: {name} must be {what} (head dims other than {HEAD_DIM_CKV}/{HEAD_DIM_KPE} and page "
+                           f"sizes other than 1 are not served), got {tuple(t.shape)}")
+    if t.numel() and (t.stride(-1) != 1 or any(t.stride(i) % 8 for i in range(t.dim() - 1)) or t.data_ptr() % 16):
+        raise RuntimeError(f"mla_prefill_paged: {name} needs a contiguous last dimension and 16-byte aligned rows, strides {t.stride()}")
+
+
+def _i32_array(name, t, device, n=None):
+    if (not torch.is_tensor(t) or t.device != device or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()
+            or (n is not None and t.numel() < n)):
+        raise RuntimeError(f"mla_prefill_paged: {name} must be a contiguous int32 vector on {device}"
+                           + (f" with at least {n} entries" if n is not None else ""))
+
+
+def mla_prefill_paged(q_nope, q_pe, ckv, kpe, qo_indptr, kv_indptr, kv_indices, kv_len_arr, causal: bool, sm_scale: float,
+                      out=None, lse=None, return_lse: bool = False):
+    """q_nope [T, H, 512], q_pe [T, H, 64], ckv [N, 512] or [N, 1, 512], kpe [N, 64] or [N, 1, 64] bf16 (any 16-byte aligned token /
+    head strides — the two column ranges of one [N, 1, 576] buffer are fine; nothing is copied); qo_indptr / kv_indptr int32 [>= B + 1],
+    kv_indices int32 (one slot = one token), kv_len_arr int32 [>= B] on the same device, B = len(qo_indptr) - 1.  Writes o [T, H, 512]
+    bf16 into `out` (allocated when None) and, with `return_lse` or `lse` given, the BASE-2 lse [T, H] f32.  Request b attends over
+    kv_len = max(0, min(kv_len_arr[b], kv_indptr[b + 1] - kv_indptr[b])) keys; `causal` is bottom-right aligned; a row that sees no key
+    gets o = 0, lse = -inf; rows of no request are left unwritten; slot indices are clamped into [0, N)."""
+    if q_nope is None or not torch.is_tensor(q_nope) or q_nope.dim() != 3:
+        raise RuntimeError("mla_prefill_paged: q_nope must be a [tokens, heads, 512] tensor")
+    T, H = q_nope.shape[:2]
+    _mla_rows("q_nope", q_nope, (T, H, HEAD_DIM_CKV), "[tokens, heads, 512]")
+    _mla_rows("q_pe", q_pe, (T, H, HEAD_DIM_KPE), "[tokens, heads, 64] with q_nope's tokens and heads")
+    dev = q_nope.device
+    if torch.is_tensor(ckv) and ckv.dim() == 3 and torch.is_tensor(kpe) and kpe.dim() == 3:
+        _mla_rows("ckv_cache", ckv, (None, 1, HEAD_DIM_CKV), "[slots, 1, 512]")
+        _mla_rows("kpe_cache", kpe, (ckv.shape[0], 1, HEAD_DIM_KPE), "[slots, 1, 64] with ckv_cache's slots")
+    else:
+        _mla_rows("ckv_cache", ckv, (None, HEAD_DIM_CKV), "[slots, 512] or [slots, 1, 512]")
+        _mla_rows("kpe_cache", kpe, (ckv.shape[0], HEAD_DIM_KPE), "[slots, 64] with ckv_cache's slots")
+    if q_pe.device != dev or ckv.device != dev or kpe.device != dev:
+        raise RuntimeError("mla_prefill_paged: q_nope, q_pe, ckv_cache and kpe_cache must sit on one device")
+    _i32_array("qo_indptr", qo_indptr, dev, 1)
+    B = qo_indptr.numel() - 1
+    _i32_array("kv_indptr", kv_indptr, dev, B + 1)
+    _i32_array("kv_indices", kv_indices, dev)
+    _i32_array("kv_len_arr", kv_len_arr, dev, B)
+    if out is None:
+        out = torch.empty(T, H, HEAD_DIM_CKV, dtype=torch.bfloat16, device=dev)
+    elif (not torch.is_tensor(out) or out.dtype != torch.bfloat16 or out.device != dev or tuple(out.shape) != (T, H, HEAD_DIM_CKV)
+          or not out.is_contiguous()):
+        raise RuntimeError(f"mla_prefill_paged: out must be a contiguous bf16 [{T}, {H}, {HEAD_DIM_CKV}] tensor on {dev}")
+    if lse is None:
+        lse = torch.empty(T, H, dtype=torch.float32, device=dev) if return_lse else None
+    elif (not torch.is_tensor(lse) or lse.dtype != torch.float32 or lse.device != dev or tuple(lse.shape) != (T, H)
+          or not lse.is_contiguous()):
+        raise RuntimeError(f"mla_prefill_paged: lse must be a contiguous f32 [{T}, {H}] tensor on {dev}")
+    a = FlMlaPrefillArgs()
+    a.struct_bytes = ctypes.sizeof(FlMlaPrefillArgs)
+    a.batch, a.num_q_tokens, a.num_kv_slots, a.num_kv_indices, a.num_heads = B, T, ckv.shape[0], kv_indices.numel(), H
+    a.head_dim_ckv, a.head_dim_kpe, a.causal, a.sm_scale = HEAD_DIM_CKV, HEAD_DIM_KPE, int(bool(causal)), float(sm_scale)
+    a.q_nope, a.q_nope_stride_token, a.q_nope_stride_head = q_nope.data_ptr(), q_nope.stride(0), q_nope.stride(1)
+    a.q_pe, a.q_pe_stride_token, a.q_pe_stride_head = q_pe.data_ptr(), q_pe.stride(0), q_pe.stride(1)
+    a.ckv, a.ckv_stride_slot, a.kpe, a.kpe_stride_slot = ckv.data_ptr(), ckv.stride(0), kpe.data_ptr(), kpe.stride(0)
+    a.qo_indptr, a.kv_indptr, a.kv_indices = qo_indptr.data_ptr(), kv_indptr.data_ptr(), kv_indices.data_ptr()
+    a.kv_len_arr, a.out, a.lse = kv_len_arr.data_ptr(), out.data_ptr(), (lse.data_ptr() if lse is not None else None)
+    check(lib.fl_mla_prefill_paged_bf16(ctypes.byref(a), stream_ptr(dev)), "fl_mla_prefill_paged_bf16")
+    return (out, lse) if return_lse else out
