@@ -44,7 +44,8 @@ typedef void* fl_stream_t;
  * 102: additive — fl_fused_add_rmsnorm_offset (GemmaRMSNorm: the 1 added in fp32), fl_mla_set_merge_timeout (+ the in-kernel split merge
  *      reports a timeout through the next fl_mla_decode call); no struct changed.
  *      (still 102, additive: fl_mha_prefill_ragged_bf16 with its own FlPrefillArgs — struct_bytes first, checked — and fl_merge_state;
- *      fl_mla_prefill_paged_bf16 with its own FlMlaPrefillArgs, struct_bytes first, checked.) */
+ *      fl_mla_prefill_paged_bf16 with its own FlMlaPrefillArgs, struct_bytes first, checked;
+ *      fl_sampling_softmax / fl_sampling_renorm / fl_sampling_sample with FlSamplingArgs, struct_bytes first, checked.) */
 #define FL_ABI_VERSION 102
 const char* fl_last_error(void);
 int fl_version(void);
@@ -498,6 +499,53 @@ typedef struct FlMlaPrefillArgs {
   float* lse;                /* f32 [T, H] contiguous, base 2; NULL = not wanted */
 } FlMlaPrefillArgs;
 int fl_mla_prefill_paged_bf16(const FlMlaPrefillArgs* args, fl_stream_t stream);
+
+/* ---- S1: flashinfer.sampling — softmax, top-k / top-p renormalisation, top-k / top-p / min-p sampling over f32 rows (csrc/sampling.hip).
+ * One workgroup per row, sort-free (radix descent on the f32 bit pattern to the row's exact cut value), one launch per call, no host
+ * synchronisation, no allocation, hipGraph-capturable.  With p(k) the k-th largest value of a row, S its sum, M(x) = sum{p_j : p_j > x}:
+ *   top-k : keep i iff p_i >= p(k) (ties at the k-th value are all kept; k >= V keeps everything; k < 1 is read as 1)
+ *   top-p : keep i iff M(p_i) < top_p * S_base (ties at the last value kept; top_p >= 1 keeps everything with p_i > 0)
+ *   FL_SAMPLING_JOINT        : the intersection, both on the input row, S_base = S       (filter_apply_order="joint")
+ *   FL_SAMPLING_TOP_K_THEN_P : top-p on the top-k survivors, S_base = the mass top-k kept  (flashinfer's default, "top_k_first")
+ *   min-p : keep i iff p_i >= min_p * max_j p_j (one f32 multiply)
+ * Entries <= 0 (and NaN) are never kept.  Per-row parameters: a nullable DEVICE pointer, indexed by the ROW of probs (as flashinfer does
+ * when `indices` maps samples to rows), or the scalar beside it when the pointer is NULL.  vocab <= 4,194,304.
+ *   fl_sampling_softmax: out[b, :] = softmax(logits[b, :] / temperature[b]) — flashinfer.sampling.softmax (srt/speculative/eagle_worker.py:308,322);
+ *                        a row of -inf gives zeros.  Reads probs (= logits), temperature / temperature_val, writes out f32 [batch, vocab].
+ *   fl_sampling_renorm : out[b, i] = p_i / S_kept for kept i, exactly 0 otherwise — top_k_renorm_prob(s) / top_p_renorm_prob(s)
+ *                        (srt/layers/sampler.py:96-97, srt/speculative/eagle_utils.py:252-263).  Modes TOP_K .. JOINT.
+ *   fl_sampling_sample : out[b] = the smallest kept i of row (indices ? indices[b] : b) whose running kept mass in vocabulary order exceeds
+ *                        u[b] * S_kept; the last kept i where f32 rounding leaves the sum below that; 0 for a row that keeps nothing —
+ *                        top_k_top_p_sampling_from_probs / min_p_sampling_from_probs (srt/layers/sampler.py:98-110).  out i32 [batch]. ---- */
+#define FL_SAMPLING_TOP_K 0
+#define FL_SAMPLING_TOP_P 1
+#define FL_SAMPLING_TOP_K_THEN_P 2
+#define FL_SAMPLING_JOINT 3
+#define FL_SAMPLING_MIN_P 4
+typedef struct FlSamplingArgs {
+  int32_t struct_bytes;      /* = sizeof(FlSamplingArgs) as the CALLER compiled it; anything else is refused */
+  int32_t mode;              /* FL_SAMPLING_* (ignored by softmax) */
+  int32_t batch;             /* B: rows written (softmax, renorm) / samples drawn */
+  int32_t vocab;             /* V */
+  int64_t num_rows;          /* rows of probs (>= B unless indices is given) */
+  int64_t row_pitch;         /* ELEMENTS between rows of probs (>= V); rows 4-byte aligned, 16-byte loads from the first aligned element */
+  const float* probs;        /* f32 [num_rows, V] at row_pitch (softmax: the logits) */
+  const int32_t* indices;    /* i32 [B] DEVICE: sample b reads row indices[b] (clamped into the rows); NULL = row b.  sample only */
+  const void* top_k;         /* i32 or i64 [num_rows] DEVICE, or NULL -> top_k_val */
+  int32_t top_k_is_i64;
+  int32_t reserved;          /* 0 */
+  int64_t top_k_val;
+  const float* top_p;        /* f32 [num_rows] DEVICE, or NULL -> top_p_val */
+  const float* min_p;        /* f32 [num_rows] DEVICE, or NULL -> min_p_val */
+  const float* temperature;  /* f32 [B] DEVICE, or NULL -> temperature_val.  softmax only */
+  const float* u;            /* f32 [B] DEVICE uniforms in [0, 1).  sample only */
+  float top_p_val, min_p_val, temperature_val;
+  int32_t reserved2;         /* 0 */
+  void* out;                 /* f32 [B, V] contiguous (softmax, renorm) / i32 [B] (sample) */
+} FlSamplingArgs;
+int fl_sampling_softmax(const FlSamplingArgs* args, fl_stream_t stream);
+int fl_sampling_renorm(const FlSamplingArgs* args, fl_stream_t stream);
+int fl_sampling_sample(const FlSamplingArgs* args, fl_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -7,14 +7,15 @@ rmsnorm / fused_add_rmsnorm / norm._rmsnorm_fused_parallel (layernorm.py:26-31,2
 two attention-wrapper classes FlashMLABackend's base class constructs (flashinfer_mla_backend.py:124-142; attention_wrappers.py):
 both LIVE: BatchPrefillWithRaggedKVCacheWrapper — the ragged bf16 MHA prefill (192/128) of the prompt path, with `merge_state` for
 its chunked-prefix form (csrc/mha_prefill_bf16.hip; lse in base 2) — and BatchMLAPagedAttentionWrapper — absorbed paged MLA attention
-(576/512, bf16, page size 1, ragged and causal; csrc/mla_prefill_bf16.hip) — and `comm.vllm_ar` (C4).  Sampling is out of scope (not named by the north star)."""
+(576/512, bf16, page size 1, ragged and causal; csrc/mla_prefill_bf16.hip) — and `comm.vllm_ar` (C4), and the submodule `sampling`
+(softmax, top-k / top-p renormalisation, top-k / top-p / min-p sampling; csrc/sampling.hip) — taken from the submodule, as the reference does."""
 from fluent_mi355.gemm import sgl_per_token_group_quant_fp8, silu_and_mul  # noqa: F401
 from fluent_mi355.router import moe_fused_gate, routing_flash, topk_softmax  # noqa: F401
 from fluent_mi355.rope import FusedSetKVBufferArg, apply_rope_with_cos_sin_cache_inplace  # noqa: F401
 
 from .attention_wrappers import BatchMLAPagedAttentionWrapper, BatchPrefillWithRaggedKVCacheWrapper  # noqa: F401
 
-from . import activation, comm, norm, quantization  # noqa: F401
+from . import activation, comm, norm, quantization, sampling  # noqa: F401
 from .norm import fused_add_rmsnorm, gemma_fused_add_rmsnorm, gemma_rmsnorm, rmsnorm  # noqa: F401
 
 import torch as _torch
