@@ -200,6 +200,28 @@ int fl_grouped_gemm_fp8(const FlGemmArgs* args, fl_stream_t stream);
 int fl_gemm_set_num_cus(int n);   /* deep_gemm.set_num_sms (srt/tbo/tbo_executor.py:129-134) */
 int fl_gemm_get_num_cus(void);
 
+/* ---- G5: bf16 grouped GEMM of the unquantised MoE experts — eps.executor.AokGroupedGemm.run
+ * (srt/layers/moe/gemms/bf16/aok.py:3,18 -> moe/executors/eps_executor.py:35,48: w13, then silu, then w2 on the rows
+ * AllToAll.dispatch grouped by expert).  out[r, n] = sum_k A[r, k] * W[e, n, k] for r in [meta[e], meta[e+1]): bf16 operands
+ * contiguous in k, fp32 accumulation, ONE rounding (RNE) to bf16.  Rows of `out` outside [meta[0], meta[E]) are never written;
+ * meta[0] may be non-zero; group bounds are clamped into [0, M].  FL_GEMM_DENSE: one group of all M rows, meta unused.
+ * K % 64 == 0, K >= 64, N % 64 == 0 — anything else is FL_ERR_UNSUPPORTED.  A, W rows 16-byte aligned, out 8-byte aligned.
+ * One launch, no host synchronisation, no allocation, hipGraph-capturable; fl_gemm_set_num_cus caps its grid as well. ---- */
+typedef struct FlGemmBf16Args {
+  int32_t struct_bytes;       /* = sizeof(FlGemmBf16Args) as the CALLER compiled it; anything else is refused */
+  int32_t mode;               /* FL_GEMM_OFFSET or FL_GEMM_DENSE */
+  int32_t num_groups;         /* E (1 for dense) */
+  int32_t N, K;               /* W is [E, N, K] bf16 */
+  int32_t tile_rows;          /* token rows per workgroup: 32 (decode: the weight stream bounds it), 128, or 0 = choose
+                               * from M / num_groups (host integers only: a captured call site sees one fixed kernel) */
+  int64_t M;                  /* rows of A / out */
+  const void* A;              /* bf16 [M, K] */
+  const void* W;              /* bf16 [E, N, K] */
+  void* out;                  /* bf16 [M, N] */
+  const int32_t* group_meta;  /* offset mode: exclusive_sum i32 [E + 1], DEVICE */
+} FlGemmBf16Args;
+int fl_grouped_gemm_bf16(const FlGemmBf16Args* args, fl_stream_t stream);
+
 /* ---- Q1/Q2: 1x128 per-token-group FP8 quantisation (flashinfer.quantization.quant_1x128,
  * moe/executors/fp8_eps_executor.py:53-55,75-77; flashinfer.sgl_per_token_group_quant_fp8,
  * dense/gemms/fp8/fp8_kernel.py:457-460).  s = max(amax, eps)/448 (fp32), q = x/s -> e4m3 (RNE).

@@ -318,6 +318,8 @@ std::atomic<int> g_num_cus_limit{0};
 
 }  // namespace
 
+int fl_gemm_cu_limit() { return g_num_cus_limit.load(); }
+
 extern "C" int fl_gemm_set_num_cus(int n) {
   FL_CHECK_ARG(n >= 0, "fl_gemm_set_num_cus: n=%d", n);
   g_num_cus_limit.store(n);

@@ -109,6 +109,8 @@ __device__ __forceinline__ bool locate_tile(const GemmParams& p, const int32_t* 
 
 }  // namespace fl_gemm
 
+// deep_gemm.set_num_sms cap in force (0 = none): every grouped-GEMM launcher reads it once, on the host (grouped_gemm_fp8.hip)
+int fl_gemm_cu_limit();
 // 256 x 256 tile kernel: many rows per group (grouped_gemm_fp8_big2.hip, round 3)
 int fl_gemm_launch_big2(const fl_gemm::GemmParams& p, const void* A, const float* As, const void* W, const float* Ws,
                         const int32_t* group_meta, hipStream_t stream);

@@ -155,6 +155,84 @@ def gemm_fp8_fp8_bf16_nt(lhs, rhs, out, pdl: bool = False) -> None:
     _gemm(MODE_DENSE, lhs, rhs, out, None)
 
 
+# ---------------------------------------------------------------------------------------------- bf16 grouped GEMM
+class FlGemmBf16Args(ctypes.Structure):
+    """Mirror of `struct FlGemmBf16Args` in include/fluent_mi355.h."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_int32), ("mode", ctypes.c_int32), ("num_groups", ctypes.c_int32),
+        ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("tile_rows", ctypes.c_int32), ("M", ctypes.c_int64),
+        ("A", ctypes.c_void_p), ("W", ctypes.c_void_p), ("out", ctypes.c_void_p), ("group_meta", ctypes.c_void_p),
+    ]
+
+
+lib.fl_grouped_gemm_bf16.argtypes = [ctypes.POINTER(FlGemmBf16Args), ctypes.c_void_p]
+lib.fl_grouped_gemm_bf16.restype = ctypes.c_int
+
+# Rows per expert from which the 128-row tile form is used.  A first guess that nobody has measured: below it the 32-row form
+# wastes no more than half of its MFMA columns on padding and streams the weights with two workgroups per CU.  Change it only
+# with a recorded timing (tools/time_grouped_bf16.py).
+_BF16_LARGE_FORM_MIN_ROWS = 64
+
+
+def _gemm_bf16(mode, a, w, out, meta, tile_rows):
+    for t, n in ((a, "lhs"), (w, "rhs"), (out, "out")):
+        _req(torch.is_tensor(t) and t.is_cuda, f"{n} must be a device tensor (no CPU fallback on this path)")
+        _req(t.dtype == torch.bfloat16 and t.is_contiguous(), f"{n} must be contiguous bfloat16")
+    _req(a.dim() == 2 and out.dim() == 2 and w.dim() == (2 if mode == MODE_DENSE else 3), "lhs [M, K], rhs [E, N, K] ([N, K] dense), out [M, N]")
+    E = 1 if mode == MODE_DENSE else w.shape[0]
+    N, K = w.shape[-2:]
+    M = a.shape[0]
+    _req(a.shape[1] == K, f"K mismatch: lhs {a.shape[1]} vs rhs {K}")
+    _req(tuple(out.shape) == (M, N), f"out must be [{M}, {N}]")
+    _req(E >= 1, "rhs has no groups")
+    _req(K >= 64 and K % 64 == 0 and N >= 64 and N % 64 == 0, f"unsupported shape: K = {K} and N = {N} must be positive multiples of 64")
+    _req(tile_rows in (None, 0, 32, 128), "tile_rows must be None, 32 or 128")
+    g = FlGemmBf16Args()
+    g.struct_bytes = ctypes.sizeof(FlGemmBf16Args)
+    g.mode, g.num_groups, g.N, g.K, g.M = mode, E, N, K, M
+    g.tile_rows = int(tile_rows or 0)
+    g.A, g.W, g.out = a.data_ptr(), w.data_ptr(), out.data_ptr()
+    if mode == MODE_OFFSET:
+        _req(torch.is_tensor(meta) and meta.is_cuda and meta.dtype == torch.int32 and meta.is_contiguous() and
+             tuple(meta.shape) == (E + 1,), f"exclusive_sum must be int32 [{E + 1}] on device")
+        g.group_meta = meta.data_ptr()
+    check(lib.fl_grouped_gemm_bf16(ctypes.byref(g), stream_ptr(a.device)), "fl_grouped_gemm_bf16")
+
+
+def m_grouped_gemm_bf16_nt_offset(a, w, out, exclusive_sum, tile_rows: Optional[int] = None) -> None:
+    """out[ex[e]:ex[e+1]] = a[ex[e]:ex[e+1]] @ w[e]^T in bf16 (fp32 accumulation, one rounding); rows outside [ex[0], ex[E]) are not
+    written.  tile_rows: 32 / 128 token rows per workgroup, None = the library chooses from M / E."""
+    _gemm_bf16(MODE_OFFSET, a, w, out, exclusive_sum, tile_rows)
+
+
+def gemm_bf16_nt(a, w, out, tile_rows: Optional[int] = None) -> None:
+    """Dense out = a @ w^T, a [M, K], w [N, K], through the same kernel (one group)."""
+    _gemm_bf16(MODE_DENSE, a, w, out, None, tile_rows)
+
+
+class AokGroupedGemm:
+    """eps.executor.AokGroupedGemm (srt/layers/moe/gemms/bf16/aok.py:18; run: moe/executors/eps_executor.py:35,48).  The signature of
+    `run` is inferred from those two call sites; both pass None as the third argument, and nothing else is served."""
+
+    def __init__(self, num_local_experts: int):
+        self.num_local_experts = int(num_local_experts)
+
+    def run(self, input, weight, third, exclusive_sum, num_tokens_hint):
+        _req(third is None, "AokGroupedGemm.run: only None is served as the third argument (both call sites pass None)")
+        _req(torch.is_tensor(weight) and weight.dim() == 3 and weight.shape[0] == self.num_local_experts,
+             f"AokGroupedGemm.run: weight must be [{self.num_local_experts}, N, K]")
+        _req(torch.is_tensor(input) and input.dim() == 2 and input.is_cuda and input.dtype == torch.bfloat16,
+             "AokGroupedGemm.run: input must be bfloat16 [M, K] on device")
+        M = input.shape[0]
+        # the form follows host integers only: a captured call site sees one fixed kernel
+        rows = min(int(num_tokens_hint), M) if num_tokens_hint is not None and int(num_tokens_hint) > 0 else M
+        tile_rows = 128 if rows >= _BF16_LARGE_FORM_MIN_ROWS * self.num_local_experts else 32
+        out = torch.empty((M, weight.shape[1]), dtype=torch.bfloat16, device=input.device)
+        _gemm_bf16(MODE_OFFSET, input, weight, out, exclusive_sum, tile_rows)
+        return out
+
+
 # ---------------------------------------------------------------------------------------------- quantisation
 def _quant(x, x_q, x_s, eps):
     _req(x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous(), "x must be contiguous bfloat16 on device")
