@@ -45,7 +45,8 @@ typedef void* fl_stream_t;
  *      reports a timeout through the next fl_mla_decode call); no struct changed.
  *      (still 102, additive: fl_mha_prefill_ragged_bf16 with its own FlPrefillArgs — struct_bytes first, checked — and fl_merge_state;
  *      fl_mla_prefill_paged_bf16 with its own FlMlaPrefillArgs, struct_bytes first, checked;
- *      fl_sampling_softmax / fl_sampling_renorm / fl_sampling_sample with FlSamplingArgs, struct_bytes first, checked.) */
+ *      fl_sampling_softmax / fl_sampling_renorm / fl_sampling_sample with FlSamplingArgs, struct_bytes first, checked;
+ *      fl_spec_verify_greedy / fl_spec_verify_sample with FlSpecVerifyArgs, struct_bytes first, checked.) */
 #define FL_ABI_VERSION 102
 const char* fl_last_error(void);
 int fl_version(void);
@@ -568,6 +569,49 @@ typedef struct FlSamplingArgs {
 int fl_sampling_softmax(const FlSamplingArgs* args, fl_stream_t stream);
 int fl_sampling_renorm(const FlSamplingArgs* args, fl_stream_t stream);
 int fl_sampling_sample(const FlSamplingArgs* args, fl_stream_t stream);
+
+/* ---- S2: speculative CHAIN verification — flashinfer.sampling.verify_chain_greedy / chain_speculative_sampling_target_only
+ * (srt/speculative/eagle_utils.py:234,273; csrc/spec_verify.hip).  Request b owns D chain positions, flat index b * D + j: candidates[b, 0]
+ * is the verified root, candidates[b, 1 .. D-1] the drafted chain.  One launch each, no host synchronisation, no allocation,
+ * hipGraph-capturable.  Both write accept_index[b, 0] = b * D, accept_index[b, j] = b * D + j for the n accepted steps j = 1 .. n,
+ * accept_token_num[b] = n, and n + 1 entries of predicts; nothing else of predicts / accept_index is written (the caller pre-fills -1).
+ *   fl_spec_verify_greedy: step j is accepted iff candidates[b, j] == target_predict[b, j - 1] and every earlier step was;
+ *                          predicts[b * D + j] = target_predict[b, j] for j = 0 .. n.
+ *   fl_spec_verify_sample: step j is accepted iff every earlier step was and, with pt = target_probs[b, j - 1, candidates[b, j]] and
+ *                          coin = uniform_samples[b, j - 1]: coin <= pt / max(threshold_acc, 1e-9) (f32 division) or pt >= threshold_single;
+ *                          a candidate outside [0, V) is rejected.  predicts[b * D + j - 1] = candidates[b, j] for j = 1 .. n.  The final token,
+ *                          predicts[b * D + n], is drawn from w_i = max(q_i - p_i, 0), q = target_probs[b, n, :], p = draft_probs[b, n, :] if
+ *                          n < D - 1 else 0 (draft_probs is then not read), the rejected token candidates[b, n + 1] (n < D - 1, in range) given
+ *                          weight 0: the smallest i with w_i > 0 whose running weight in vocabulary order exceeds uniform_final[b] * sum(w);
+ *                          the last i with w_i > 0 where f32 rounding leaves the running sum below that; 0 when every weight is zero (the
+ *                          conventions of fl_sampling_sample).  DIFFERENCE from upstream flashinfer: upstream zeroes the rejected token's
+ *                          entry of draft_probs in place; here draft_probs is READ ONLY and never modified.
+ *                          The row is split over num_slices workgroups per request; the last to arrive (a ticket per request) finishes, in
+ *                          slice order: the result does not depend on arrival order.  The kernel leaves every ticket at 0. ---- */
+typedef struct FlSpecVerifyArgs {
+  int32_t struct_bytes;            /* = sizeof(FlSpecVerifyArgs) as the CALLER compiled it; anything else is refused */
+  int32_t batch;                   /* B <= 65535 */
+  int32_t num_draft;               /* D, 1 .. 32 */
+  int32_t vocab;                   /* V <= 4,194,304.  sample only */
+  int32_t num_slices;              /* S, 1 .. 512: workgroups per request.  sample only */
+  int32_t target_predict_is_i64;   /* greedy only */
+  int64_t accept_index_pitch;      /* ELEMENTS between rows of accept_index (>= D) */
+  int32_t* predicts;               /* i32 [B * D] */
+  int32_t* accept_index;           /* i32 [B, >= D] at accept_index_pitch */
+  int32_t* accept_token_num;       /* i32 [B] */
+  const int32_t* candidates;       /* i32 [B, D] contiguous */
+  const void* target_predict;      /* i32 or i64 [B, D] contiguous.  greedy only */
+  const float* uniform_samples;    /* f32 [B, D] contiguous.  sample only (as everything below) */
+  const float* uniform_final;      /* f32 [B] */
+  const float* target_probs;       /* f32 [B, D, V]: element (b, j, i) at b * target_pitch_b + j * target_pitch_d + i; rows 4-byte aligned */
+  const float* draft_probs;        /* f32 [B, D, V] at draft_pitch_b / draft_pitch_d; read only */
+  int64_t target_pitch_b, target_pitch_d, draft_pitch_b, draft_pitch_d;   /* ELEMENTS; pitch_d >= V */
+  float threshold_single, threshold_acc;
+  float* slice_sums;               /* f32 [B, S] workspace, any contents; may be NULL when S = 1 */
+  uint32_t* tickets;               /* u32 [B] workspace, ALL ZERO on entry and on exit, not shared with a launch on another stream; NULL when S = 1 */
+} FlSpecVerifyArgs;
+int fl_spec_verify_greedy(const FlSpecVerifyArgs* args, fl_stream_t stream);
+int fl_spec_verify_sample(const FlSpecVerifyArgs* args, fl_stream_t stream);
 
 #ifdef __cplusplus
 }
