@@ -223,12 +223,63 @@ typedef struct FlGemmBf16Args {
 } FlGemmBf16Args;
 int fl_grouped_gemm_bf16(const FlGemmBf16Args* args, fl_stream_t stream);
 
+/* ---- G6: W8A8 dense GEMM, scales applied once after the product — flashinfer.fp8_scaled_mm
+ * (srt/layers/dense/gemms/fp8/fp8_utils.py:434,605 apply_fp8_linear; layouts/w8a8_fp8.py) and flashinfer.int8_scaled_mm
+ * (layouts/w8a8_int8.py:203-216; compressed_tensors_w8a8_int8.py:167-169):
+ *     out[m, n] = out_type( f32( sum_k A[m, k] * B[n, k] ) * sa[m] * sb[n] + bias[n] )
+ * A [M, K] and B [N, K] (the weight as stored) hold one byte per element, k contiguous, rows lda / ldb bytes apart; the int8
+ * accumulator is i32 (exact) and becomes f32 only in the epilogue.  sa / sb: f32, one entry per row / column (stride 1) or ONE
+ * entry (stride 0).  bias: NULL or [N] in the output type.  out: bf16 / fp16, rows ldc elements apart; rows >= M and columns >= N
+ * are never written.  K % 16 == 0, N % 16 == 0, lda % 16 == 0, ldb % 16 == 0, ldc % 4 == 0, A / B 16-byte and out 8-byte
+ * aligned; M == 0 returns without a launch; anything else is FL_ERR_INVALID before any launch.  A k tail shorter than the MFMA's
+ * k step is zero-filled in LDS (never read past the row).  One launch, no host synchronisation, no allocation,
+ * hipGraph-capturable (csrc/gemm_w8a8.hip). ---- */
+#define FL_W8A8_FP8_E4M3 0
+#define FL_W8A8_INT8 1
+#define FL_W8A8_OUT_BF16 0
+#define FL_W8A8_OUT_FP16 1
+typedef struct FlGemmW8A8Args {
+  int32_t struct_bytes;       /* = sizeof(FlGemmW8A8Args) as the CALLER compiled it; anything else is refused */
+  int32_t elem_type;          /* FL_W8A8_FP8_E4M3 (OCP e4m3fn) or FL_W8A8_INT8 */
+  int32_t out_type;           /* FL_W8A8_OUT_BF16 or FL_W8A8_OUT_FP16 */
+  int32_t tile_rows;          /* token rows per workgroup: 32 (decode: a weight stream, 64-column tiles), 128 (128 x 128 tiles),
+                               * or 0 = choose from M (host integers only: a captured call site sees one fixed kernel) */
+  int32_t N, K;
+  int64_t M;
+  int64_t lda, ldb;           /* bytes between rows of A / B */
+  int64_t ldc;                /* elements between rows of out */
+  int64_t sa_stride, sb_stride; /* 1, or 0 for a single broadcast entry */
+  const void* A;
+  const void* B;
+  const float* sa;
+  const float* sb;
+  const void* bias;
+  void* out;
+} FlGemmW8A8Args;
+int fl_gemm_w8a8(const FlGemmW8A8Args* args, fl_stream_t stream);
+
 /* ---- Q1/Q2: 1x128 per-token-group FP8 quantisation (flashinfer.quantization.quant_1x128,
  * moe/executors/fp8_eps_executor.py:53-55,75-77; flashinfer.sgl_per_token_group_quant_fp8,
  * dense/gemms/fp8/fp8_kernel.py:457-460).  s = max(amax, eps)/448 (fp32), q = x/s -> e4m3 (RNE).
  * x bf16 [M, K]; scale (m, kb) written at m*s_stride_m + kb*s_stride_k. ---- */
 int fl_quant_1x128(const void* x, int64_t M, int K, float eps, void* x_q, float* x_s, int64_t s_stride_m,
                    int64_t s_stride_k, fl_stream_t stream);
+
+/* ---- Q3-Q5: the row / tensor quantisers of the W8A8 path.  x is contiguous bf16; one wave per row (or group), 16-byte loads;
+ * every scale is computed in f32 and the quotient x / s is the IEEE one.  All capturable, no host synchronisation.
+ * fl_quant_per_token_fp8 — flashinfer.sgl_per_token_quant_fp8 (dense/gemms/fp8/fp8_kernel.py:43-47; fp8_utils.py apply_fp8_linear):
+ *   s[m] = max(amax_m, 1e-10) / 448, q = e4m3fn(x / s) saturating at +-448; an all-zero row gives zeros and s = 1e-10 / 448.  K % 8 == 0.
+ * fl_quant_per_token_group_int8 — flashinfer.sgl_per_token_group_quant_int8 (layouts/w8a8_int8.py:203-216 per_token_quant_int8 with
+ *   group_size = K; apply_w8a8_block_int8_linear with group_size = 128): s[m, g] = max(amax, eps) / 127 at x_s[m * (K / group) + g],
+ *   q = clamp(round-half-away(x / s), -127, 127).  group_size % 8 == 0, K % group_size == 0.
+ * fl_quant_per_tensor_fp8 — flashinfer.sgl_per_tensor_quant_fp8 (fp8_kernel.py:43-47): is_static = 0: x_s[0] = max(amax, 1e-10) / 448
+ *   over ALL numel elements (a clear kernel, then a vector atomic max on the non-negative f32 bit pattern of each wave's scale —
+ *   division by 448 is monotone, so the maximum of the scales is the scale of the maximum), then the quantise launch: three
+ *   launches and no memset node.  is_static != 0: one launch that reads x_s[0].  numel % 8 == 0. ---- */
+int fl_quant_per_token_fp8(const void* x, int64_t M, int K, void* x_q, float* x_s, fl_stream_t stream);
+int fl_quant_per_token_group_int8(const void* x, int64_t M, int K, int group_size, float eps, void* x_q, float* x_s,
+                                  fl_stream_t stream);
+int fl_quant_per_tensor_fp8(const void* x, int64_t numel, void* x_q, float* x_s, int is_static, fl_stream_t stream);
 
 /* ---- A1: silu(x[:, :I]) * x[:, I:] (eps.executor.silu, fp8_eps_executor.py:62; flashinfer.silu_and_mul), bf16;
  * with q_out != NULL also emits the 1x128 quantisation of the result

@@ -7,6 +7,7 @@
 //                      python/sglang/srt/layers/activation.py:58-60 (silu in the bf16 domain: F.silu rounds to bf16,
 //                      then a bf16 multiply), fused variant == flashinfer.activation.silu_and_mul_fuse_block_quant
 //                      (activation.py:73, deep_ep_executor.py:676)
+//   fl_quant_per_token_fp8 / fl_quant_per_token_group_int8 / fl_quant_per_tensor_fp8: the W8A8 quantisers (one wave per row; below)
 // HBM-bound elementwise work: 16 lanes per 128-element group (8 bf16 = 16 B per lane), 4 groups per wave, amax by
 // 4 DPP/shuffle steps inside the 16-lane group.  No LDS.
 #include "fl_common.h"
@@ -115,6 +116,68 @@ unsigned grid_for(long long groups) {
   return (unsigned)blocks;
 }
 
+// ---- Q3-Q5: per-token / per-group / per-tensor quantisers of the W8A8 path (csrc/gemm_w8a8.hip consumes them) ----
+// eight quotients x / s -> int8 by round-half-away, clamped to +-127 (layouts/w8a8_int8.py per_token_quant_int8)
+__device__ __forceinline__ uint2 quant8_i8(const float (&v)[8], const float s) {
+  uint32_t b[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) b[i] = (uint32_t)(int)fminf(fmaxf(roundf(v[i] / s), -127.f), 127.f) & 0xffu;
+  return make_uint2(b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24), b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24));
+}
+
+// One wave per row of G elements (a token, or one 1 x G group of it): amax over 16-byte loads, one wave reduction, then the quantise
+// pass reads the row again (it is at most a few KiB: an L1 / L2 hit).  s = max(amax, eps) / qmax in f32, q = x / s (IEEE).
+template <bool kInt8>
+__global__ __launch_bounds__(256) void quant_rows_kernel(const uint16_t* __restrict__ x, long long rows, int G, float eps,
+                                                         uint8_t* __restrict__ q, float* __restrict__ s) {
+  const int lane = threadIdx.x & 63;
+  for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (long long)gridDim.x * 4) {   // (wave-uniform)
+    const uint16_t* xr = x + r * G;
+    float v[8];
+    float amax = 0.f;
+    for (int c = lane * 8; c < G; c += 512) {
+      unpack8(*reinterpret_cast<const uint4*>(xr + c), v);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
+    }
+    amax = fl_wave_max(amax);
+    const float sc = fmaxf(amax, eps) / (kInt8 ? 127.f : FL_FP8_MAX);
+    for (int c = lane * 8; c < G; c += 512) {
+      unpack8(*reinterpret_cast<const uint4*>(xr + c), v);
+      *reinterpret_cast<uint2*>(q + r * G + c) = kInt8 ? quant8_i8(v, sc) : quant8(v, sc);
+    }
+    if (lane == 0) s[r] = sc;
+  }
+}
+
+__global__ void clear_f32_kernel(float* p) { *p = 0.f; }   // (not a memset node: the call must replay inside a captured graph)
+
+// per-tensor dynamic scale: every wave folds max(amax, 1e-10) / 448 of its chunks into *s by a vector atomic max on the bit pattern
+// (non-negative f32 order like unsigned integers; the division is monotone, so max of the scales = scale of the max, bit for bit)
+__global__ __launch_bounds__(256) void absmax_scale_kernel(const uint16_t* __restrict__ x, long long chunks, float* s) {
+  float v[8];
+  float amax = 0.f;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (long long)gridDim.x * 256) {
+    unpack8(*reinterpret_cast<const uint4*>(x + c * 8), v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
+  }
+  amax = fl_wave_max(amax);
+  if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned int*>(s), __float_as_uint(fmaxf(amax, 1e-10f) / FL_FP8_MAX));
+}
+
+__global__ __launch_bounds__(256) void quant_flat_fp8_kernel(const uint16_t* __restrict__ x, long long chunks, uint8_t* __restrict__ q,
+                                                             const float* __restrict__ s) {
+  const float sc = *s;
+  float v[8];
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (long long)gridDim.x * 256) {
+    unpack8(*reinterpret_cast<const uint4*>(x + c * 8), v);
+    *reinterpret_cast<uint2*>(q + c * 8) = quant8(v, sc);
+  }
+}
+
+unsigned grid_capped(long long blocks) { return (unsigned)(blocks > 2048 ? 2048 : blocks < 1 ? 1 : blocks); }
+
 }  // namespace
 
 extern "C" int fl_quant_1x128(const void* x, int64_t M, int K, float eps, void* x_q, float* x_s, int64_t s_stride_m,
@@ -156,5 +219,48 @@ extern "C" int fl_silu_and_mul_masked(const void* x, int num_groups, int64_t row
   silu_mul_kernel<true><<<dim3(grid_for(M * (I / 128))), dim3(256), 0, (hipStream_t)stream>>>(
       (const uint16_t*)x, M, I, nullptr, (uint8_t*)q_out, s_out, s_stride_m, s_stride_k, masked_m, rows_per_group, s_stride_g);
   FL_CHECK_LAUNCH("fl_silu_and_mul_masked");
+  return FL_OK;
+}
+
+extern "C" int fl_quant_per_token_fp8(const void* x, int64_t M, int K, void* x_q, float* x_s, fl_stream_t stream) {
+  FL_CHECK_ARG(M >= 0 && K > 0 && K % 8 == 0, "fl_quant_per_token_fp8: K=%d must be a positive multiple of 8", K);
+  if (M == 0) return FL_OK;
+  FL_CHECK_ARG(x && x_q && x_s, "fl_quant_per_token_fp8: null pointer");
+  FL_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)x_q % 8) == 0, "fl_quant_per_token_fp8: x must be 16-byte, x_q 8-byte aligned");
+  quant_rows_kernel<false><<<dim3(grid_capped((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>((const uint16_t*)x, M, K, 1e-10f,
+                                                                                              (uint8_t*)x_q, x_s);
+  FL_CHECK_LAUNCH("fl_quant_per_token_fp8");
+  return FL_OK;
+}
+
+extern "C" int fl_quant_per_token_group_int8(const void* x, int64_t M, int K, int group_size, float eps, void* x_q, float* x_s,
+                                             fl_stream_t stream) {
+  FL_CHECK_ARG(M >= 0 && K > 0 && group_size > 0 && group_size % 8 == 0 && K % group_size == 0,
+               "fl_quant_per_token_group_int8: K=%d, group_size=%d (group_size a multiple of 8 that divides K)", K, group_size);
+  FL_CHECK_ARG(eps > 0.f, "fl_quant_per_token_group_int8: eps must be positive");
+  if (M == 0) return FL_OK;
+  FL_CHECK_ARG(x && x_q && x_s, "fl_quant_per_token_group_int8: null pointer");
+  FL_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)x_q % 8) == 0, "fl_quant_per_token_group_int8: x must be 16-byte, x_q 8-byte aligned");
+  const long long rows = M * (K / group_size);
+  quant_rows_kernel<true><<<dim3(grid_capped((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>((const uint16_t*)x, rows, group_size,
+                                                                                                eps, (uint8_t*)x_q, x_s);
+  FL_CHECK_LAUNCH("fl_quant_per_token_group_int8");
+  return FL_OK;
+}
+
+extern "C" int fl_quant_per_tensor_fp8(const void* x, int64_t numel, void* x_q, float* x_s, int is_static, fl_stream_t stream) {
+  FL_CHECK_ARG(numel >= 0 && numel % 8 == 0, "fl_quant_per_tensor_fp8: numel=%lld must be a multiple of 8", (long long)numel);
+  FL_CHECK_ARG(x_s != nullptr, "fl_quant_per_tensor_fp8: null scale pointer");
+  FL_CHECK_ARG(numel == 0 || (x && x_q), "fl_quant_per_tensor_fp8: null pointer");
+  FL_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)x_q % 8) == 0, "fl_quant_per_tensor_fp8: x must be 16-byte, x_q 8-byte aligned");
+  const long long chunks = numel / 8;
+  const dim3 grid(grid_capped((chunks + 255) / 256)), block(256);
+  const hipStream_t s = (hipStream_t)stream;
+  if (!is_static) {
+    clear_f32_kernel<<<dim3(1), dim3(1), 0, s>>>(x_s);
+    absmax_scale_kernel<<<grid, block, 0, s>>>((const uint16_t*)x, chunks, x_s);
+  }
+  if (numel > 0) quant_flat_fp8_kernel<<<grid, block, 0, s>>>((const uint16_t*)x, chunks, (uint8_t*)x_q, x_s);
+  FL_CHECK_LAUNCH("fl_quant_per_tensor_fp8");
   return FL_OK;
 }

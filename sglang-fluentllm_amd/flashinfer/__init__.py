@@ -10,6 +10,9 @@ its chunked-prefix form (csrc/mha_prefill_bf16.hip; lse in base 2) — and Batch
 (576/512, bf16, page size 1, ragged and causal; csrc/mla_prefill_bf16.hip) — and `comm.vllm_ar` (C4), and the submodule `sampling`
 (softmax, top-k / top-p renormalisation, top-k / top-p / min-p sampling; csrc/sampling.hip) — taken from the submodule, as the reference does."""
 from fluent_mi355.gemm import sgl_per_token_group_quant_fp8, silu_and_mul  # noqa: F401
+# the W8A8 dense path (per-token x per-channel scales, csrc/gemm_w8a8.hip + the row quantisers of csrc/quant_act.hip)
+from fluent_mi355.gemm import (fp8_scaled_mm, int8_scaled_mm, sgl_per_tensor_quant_fp8, sgl_per_token_group_quant_int8,  # noqa: F401
+                               sgl_per_token_quant_fp8)
 from fluent_mi355.router import moe_fused_gate, routing_flash, topk_softmax  # noqa: F401
 from fluent_mi355.rope import FusedSetKVBufferArg, apply_rope_with_cos_sin_cache_inplace  # noqa: F401
 

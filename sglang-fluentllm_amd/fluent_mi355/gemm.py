@@ -233,6 +233,141 @@ class AokGroupedGemm:
         return out
 
 
+# ---------------------------------------------------------------------------------------------- W8A8 dense GEMM
+class FlGemmW8A8Args(ctypes.Structure):
+    """Mirror of `struct FlGemmW8A8Args` in include/fluent_mi355.h."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_int32), ("elem_type", ctypes.c_int32), ("out_type", ctypes.c_int32),
+        ("tile_rows", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("M", ctypes.c_int64),
+        ("lda", ctypes.c_int64), ("ldb", ctypes.c_int64), ("ldc", ctypes.c_int64),
+        ("sa_stride", ctypes.c_int64), ("sb_stride", ctypes.c_int64),
+        ("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("sa", ctypes.c_void_p), ("sb", ctypes.c_void_p),
+        ("bias", ctypes.c_void_p), ("out", ctypes.c_void_p),
+    ]
+
+
+lib.fl_gemm_w8a8.argtypes = [ctypes.POINTER(FlGemmW8A8Args), ctypes.c_void_p]
+lib.fl_gemm_w8a8.restype = ctypes.c_int
+lib.fl_quant_per_token_fp8.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+lib.fl_quant_per_token_fp8.restype = ctypes.c_int
+lib.fl_quant_per_token_group_int8.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+lib.fl_quant_per_token_group_int8.restype = ctypes.c_int
+lib.fl_quant_per_tensor_fp8.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+lib.fl_quant_per_tensor_fp8.restype = ctypes.c_int
+
+_W8A8_OUT = {torch.bfloat16: 0, torch.float16: 1}
+
+
+def _w8a8_scale(t, n, name):
+    _req(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32, f"{name} must be a float32 device tensor")
+    _req(t.numel() in (1, n) and (t.dim() <= 1 or (t.dim() == 2 and t.shape[1] == 1)) and t.is_contiguous(),
+         f"{name} must hold {n} entries or 1, shaped [{n}] or [{n}, 1], contiguous")
+    return 0 if t.numel() == 1 and n != 1 else 1
+
+
+def gemm_w8a8_nt(elem_dtype, mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None, out=None, tile_rows: Optional[int] = None):
+    """out[M, N] = out_dtype(f32(mat_a @ mat_b) * scales_a[m] * scales_b[n] + bias[n]) on csrc/gemm_w8a8.hip.  mat_a [M, K] with
+    stride(1) == 1 (any 16-byte-multiple row stride), mat_b [K, N] with stride(0) == 1 (the [N, K] weight, transposed view).  `out`:
+    an [M, N] view (stride(1) == 1) to write into instead of a fresh tensor; tile_rows: 32 / 128 forces the decode / compute form."""
+    name = "fp8_scaled_mm" if elem_dtype == torch.float8_e4m3fn else "int8_scaled_mm"
+    for t, n in ((mat_a, "mat_a"), (mat_b, "mat_b")):
+        _req(torch.is_tensor(t) and t.is_cuda, f"{name}: {n} must be a device tensor (no CPU fallback on this path)")
+        _req(t.dtype == elem_dtype and t.dim() == 2, f"{name}: {n} must be a 2-d {elem_dtype} tensor")
+    _req(out_dtype in _W8A8_OUT, f"{name}: out_dtype must be bfloat16 or float16")
+    M, K = mat_a.shape
+    _req(mat_b.shape[0] == K, f"{name}: mat_b must be [K = {K}, N]")
+    N = mat_b.shape[1]
+    _req(K % 16 == 0 and N % 16 == 0 and K > 0 and N > 0, f"{name}: mat_b: K = {K} and N = {N} must be positive multiples of 16")
+    _req(mat_b.stride(0) == 1 and mat_b.stride(1) >= K and mat_b.stride(1) % 16 == 0,
+         f"{name}: mat_b must be column-major (stride(0) == 1: the [N, K] weight transposed)")
+    _req(mat_a.stride(1) == 1 and (M <= 1 or (mat_a.stride(0) >= K and mat_a.stride(0) % 16 == 0)),
+         f"{name}: mat_a must be row-major (stride(1) == 1) with a row stride that is a multiple of 16")
+    g = FlGemmW8A8Args()
+    g.struct_bytes = ctypes.sizeof(FlGemmW8A8Args)
+    g.sa_stride = _w8a8_scale(scales_a, M, f"{name}: scales_a") if M > 0 else 1
+    g.sb_stride = _w8a8_scale(scales_b, N, f"{name}: scales_b")
+    if bias is not None:
+        _req(torch.is_tensor(bias) and bias.is_cuda and bias.dtype == out_dtype and tuple(bias.shape) == (N,) and bias.is_contiguous(),
+             f"{name}: bias must be a contiguous {out_dtype} [{N}] device tensor")
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype, device=mat_a.device)
+    else:
+        _req(torch.is_tensor(out) and out.is_cuda and out.dtype == out_dtype and tuple(out.shape) == (M, N) and
+             out.stride(1) == 1 and (M <= 1 or out.stride(0) % 4 == 0), f"{name}: out must be a {out_dtype} [{M}, {N}] view with stride(1) == 1")
+    _req(tile_rows in (None, 0, 32, 128), f"{name}: tile_rows must be None, 32 or 128")
+    g.elem_type = 0 if elem_dtype == torch.float8_e4m3fn else 1
+    g.out_type = _W8A8_OUT[out_dtype]
+    g.tile_rows = int(tile_rows or 0)
+    g.M, g.N, g.K = M, N, K
+    g.lda, g.ldc = (mat_a.stride(0), out.stride(0)) if M > 1 else (K, N)   # (a single row has no meaningful row stride)
+    g.ldb = mat_b.stride(1)
+    g.A, g.B, g.sa, g.sb, g.out = mat_a.data_ptr(), mat_b.data_ptr(), scales_a.data_ptr(), scales_b.data_ptr(), out.data_ptr()
+    g.bias = bias.data_ptr() if bias is not None else None
+    check(lib.fl_gemm_w8a8(ctypes.byref(g), stream_ptr(mat_a.device)), "fl_gemm_w8a8")
+    return out
+
+
+def fp8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None):
+    """flashinfer.fp8_scaled_mm (dense/gemms/fp8/fp8_utils.py:434,605): e4m3fn x e4m3fn, per-token x per-channel (or per-tensor) scales."""
+    return gemm_w8a8_nt(torch.float8_e4m3fn, mat_a, mat_b, scales_a, scales_b, out_dtype, bias)
+
+
+def int8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None):
+    """flashinfer.int8_scaled_mm (layouts/w8a8_int8.py:203-216): int8 x int8 with an exact i32 accumulator, same scales."""
+    return gemm_w8a8_nt(torch.int8, mat_a, mat_b, scales_a, scales_b, out_dtype, bias)
+
+
+def _quant_in(x, x_q, q_dtype, name):
+    _req(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() >= 1,
+         f"{name}: input must be contiguous bfloat16 on device")
+    _req(torch.is_tensor(x_q) and x_q.is_cuda and x_q.dtype == q_dtype and x_q.is_contiguous() and x_q.shape == x.shape,
+         f"{name}: output_q must be contiguous {q_dtype} of the input's shape on device")
+
+
+def _quant_scale(s, n, name):
+    _req(torch.is_tensor(s) and s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() and s.numel() == n,
+         f"{name}: output_s must be contiguous float32 with {n} entries on device")
+
+
+def sgl_per_token_quant_fp8(input, output_q, output_s) -> None:
+    """flashinfer.sgl_per_token_quant_fp8 (fp8_kernel.py:43-47): output_s [M, 1] = max(amax, 1e-10) / 448, output_q = e4m3fn(x / s)."""
+    _quant_in(input, output_q, torch.float8_e4m3fn, "sgl_per_token_quant_fp8")
+    K = input.shape[-1]
+    M = input.numel() // K if K else 0
+    _req(K > 0 and K % 8 == 0, f"sgl_per_token_quant_fp8: input: K = {K} must be a positive multiple of 8")
+    _quant_scale(output_s, M, "sgl_per_token_quant_fp8")
+    check(lib.fl_quant_per_token_fp8(input.data_ptr(), M, K, output_q.data_ptr(), output_s.data_ptr(), stream_ptr(input.device)),
+          "fl_quant_per_token_fp8")
+
+
+def sgl_per_token_group_quant_int8(input, output_q, output_s, group_size, eps, int8_min, int8_max) -> None:
+    """flashinfer.sgl_per_token_group_quant_int8: output_s [M, K / group_size] = max(amax, eps) / 127, output_q = round-half-away(x / s)
+    (|q| <= 127); group_size = K is per_token_quant_int8 (layouts/w8a8_int8.py), 128 the groups of apply_w8a8_block_int8_linear."""
+    _quant_in(input, output_q, torch.int8, "sgl_per_token_group_quant_int8")
+    K = input.shape[-1]
+    group_size = int(group_size)
+    _req(group_size > 0 and group_size % 8 == 0 and K % group_size == 0,
+         f"sgl_per_token_group_quant_int8: group_size = {group_size} must be a multiple of 8 that divides K = {K}")
+    _req(int(int8_max) == 127 and int(int8_min) in (-128, -127) and float(eps) > 0,
+         "sgl_per_token_group_quant_int8: int8_max must be 127, int8_min -128 or -127 (the quotient never leaves +-127), eps > 0")
+    M = input.numel() // K
+    _quant_scale(output_s, M * (K // group_size), "sgl_per_token_group_quant_int8")
+    check(lib.fl_quant_per_token_group_int8(input.data_ptr(), M, K, group_size, float(eps), output_q.data_ptr(), output_s.data_ptr(),
+                                            stream_ptr(input.device)), "fl_quant_per_token_group_int8")
+
+
+def sgl_per_tensor_quant_fp8(input, output_q, output_s, is_static) -> None:
+    """flashinfer.sgl_per_tensor_quant_fp8 (fp8_kernel.py:43-47): is_static False writes output_s[0] = max(amax, 1e-10) / 448 first
+    (whatever it held), True reads it; output_q = e4m3fn(x / output_s), saturating."""
+    _quant_in(input, output_q, torch.float8_e4m3fn, "sgl_per_tensor_quant_fp8")
+    _req(input.numel() % 8 == 0, "sgl_per_tensor_quant_fp8: input: numel must be a multiple of 8")
+    _quant_scale(output_s, 1, "sgl_per_tensor_quant_fp8")
+    check(lib.fl_quant_per_tensor_fp8(input.data_ptr(), input.numel(), output_q.data_ptr(), output_s.data_ptr(), int(bool(is_static)),
+                                      stream_ptr(input.device)), "fl_quant_per_tensor_fp8")
+
+
 # ---------------------------------------------------------------------------------------------- quantisation
 def _quant(x, x_q, x_s, eps):
     _req(x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous(), "x must be contiguous bfloat16 on device")
