@@ -46,7 +46,8 @@ typedef void* fl_stream_t;
  *      (still 102, additive: fl_mha_prefill_ragged_bf16 with its own FlPrefillArgs — struct_bytes first, checked — and fl_merge_state;
  *      fl_mla_prefill_paged_bf16 with its own FlMlaPrefillArgs, struct_bytes first, checked;
  *      fl_sampling_softmax / fl_sampling_renorm / fl_sampling_sample with FlSamplingArgs, struct_bytes first, checked;
- *      fl_spec_verify_greedy / fl_spec_verify_sample with FlSpecVerifyArgs, struct_bytes first, checked.) */
+ *      fl_spec_verify_greedy / fl_spec_verify_sample with FlSpecVerifyArgs, struct_bytes first, checked;
+ *      fl_gqa_paged_attention_bf16 with FlGqaPagedArgs, struct_bytes first, checked.) */
 #define FL_ABI_VERSION 102
 const char* fl_last_error(void);
 int fl_version(void);
@@ -663,6 +664,50 @@ typedef struct FlSpecVerifyArgs {
 } FlSpecVerifyArgs;
 int fl_spec_verify_greedy(const FlSpecVerifyArgs* args, fl_stream_t stream);
 int fl_spec_verify_sample(const FlSpecVerifyArgs* args, fl_stream_t stream);
+
+/* ---- P3: paged GQA attention over token-indexed KV, head dim 128, bf16 — flashinfer.BatchDecodeWithPagedKVCacheWrapper /
+ * BatchPrefillWithPagedKVCacheWrapper with page size 1 and BatchPrefillWithRaggedKVCacheWrapper at 128/128
+ * (srt/layers/attention/flashinfer_backend.py; csrc/gqa_paged_bf16.hip).  Per request b (query tokens qo_indptr[b] .. qo_indptr[b+1], or
+ * the single token b when qo_indptr is NULL; key j lives in slot kv_indices[kv_indptr[b] + j], or in row kv_indptr[b] + j of k / v
+ * themselves when kv_indices is NULL; kv_len = kv_indptr[b+1] - kv_indptr[b]), token i and query head h, with KV head h / G,
+ * G = num_qo_heads / num_kv_heads:  o = softmax(sm_scale q k^T + mask) v, bf16 operands, fp32 accumulation, bf16 P.  causal: bottom-right
+ * aligned — token i sees keys j <= i + (kv_len - q_len).  lse (optional) is BASE 2, as fl_merge_state reads it.  A row without a visible
+ * key gets o = 0, lse = -inf; rows of `out` that belong to no request are not written.  Strides in ELEMENTS, last dimension contiguous,
+ * rows 16-byte aligned; qo_indptr values are clamped to [0, num_q_tokens], kv_indptr values to [0, num_kv_indices], slot indices to
+ * [0, num_kv_slots).  Everything that depends on lengths is read on the device: no host synchronisation, hipGraph-capturable.
+ *   decode_form = 0: 128 (token, head-of-group) rows per workgroup, any q_len.
+ *   decode_form = 1: the CALLER asserts q_len * G <= 16 for every request (tokens past that are not served: left unwritten); the waves of
+ *                    a workgroup split the KV, and the KV of a request is cut into num_splits slices (1 .. 16), one workgroup each, whose
+ *                    partial states land in `workspace` and are merged by a second kernel in slice order (deterministic).
+ *                    workspace_bytes >= num_splits * num_q_tokens * num_qo_heads * 129 * 4 when num_splits > 1. ---- */
+typedef struct FlGqaPagedArgs {
+  int32_t struct_bytes;      /* = sizeof(FlGqaPagedArgs) as the CALLER compiled it; anything else is refused */
+  int32_t batch;             /* B: requests */
+  int64_t num_q_tokens;      /* T: rows of q / out / lse */
+  int64_t num_kv_slots;      /* N: rows of k / v */
+  int64_t num_kv_indices;    /* entries of kv_indices (kv_indices NULL: = N) */
+  int32_t num_qo_heads, num_kv_heads;   /* Hq % Hkv == 0 */
+  int32_t head_dim;          /* 128 */
+  int32_t causal;
+  float sm_scale;
+  int32_t decode_form;       /* 0 / 1, see above */
+  int32_t num_splits;        /* S, decode form only; row form: 1 */
+  int32_t reserved;          /* 0 */
+  const void* q;             /* bf16 [T, Hq, 128] */
+  int64_t q_stride_token, q_stride_head;
+  const void* k;             /* bf16 [N, Hkv, 128] */
+  int64_t k_stride_slot, k_stride_head;
+  const void* v;             /* bf16 [N, Hkv, 128] */
+  int64_t v_stride_slot, v_stride_head;
+  const int32_t* qo_indptr;  /* i32 [B + 1], DEVICE; NULL = one query token per request (T == B) */
+  const int32_t* kv_indptr;  /* i32 [B + 1], DEVICE */
+  const int32_t* kv_indices; /* i32 [num_kv_indices], DEVICE; NULL = identity (the ragged form) */
+  void* out;                 /* bf16 [T, Hq, 128] contiguous */
+  float* lse;                /* f32 [T, Hq] contiguous, base 2; NULL = not wanted */
+  void* workspace;           /* DEVICE, 16-byte aligned, any contents; may be NULL when num_splits == 1 */
+  int64_t workspace_bytes;
+} FlGqaPagedArgs;
+int fl_gqa_paged_attention_bf16(const FlGqaPagedArgs* args, fl_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -17,8 +17,12 @@ from fluent_mi355.router import moe_fused_gate, routing_flash, topk_softmax  # n
 from fluent_mi355.rope import FusedSetKVBufferArg, apply_rope_with_cos_sin_cache_inplace  # noqa: F401
 
 from .attention_wrappers import BatchMLAPagedAttentionWrapper, BatchPrefillWithRaggedKVCacheWrapper  # noqa: F401
+# the GQA models' default attention backend (srt/layers/attention/flashinfer_backend.py): paged GQA attention, head dim 128, bf16, page
+# size 1 (csrc/gqa_paged_bf16.hip), with the host helpers of `decode` and `cascade` that file imports
+from .attention_wrappers import (BatchDecodeWithPagedKVCacheWrapper, BatchPrefillWithPagedKVCacheWrapper,  # noqa: F401
+                                 run_device_plan_prefill_graph)
 
-from . import activation, comm, norm, quantization, sampling  # noqa: F401
+from . import activation, cascade, comm, decode, norm, quantization, sampling  # noqa: F401
 from .norm import fused_add_rmsnorm, gemma_fused_add_rmsnorm, gemma_rmsnorm, rmsnorm  # noqa: F401
 
 import torch as _torch

@@ -2,7 +2,10 @@
 `flashinfer.BatchPrefillWithRaggedKVCacheWrapper.forward / forward_return_lse` (srt/layers/attention/flashinfer_mla_backend.py:449,
 layers/attention/chunker.py:304) and `flashinfer.merge_state` (models/deepseek_v2.py:1037-1071) run on the DeepSeek-V3 / LongCat MLA
 prompt path — and absorbed paged MLA attention over token-indexed KV (csrc/mla_prefill_bf16.hip), what
-`flashinfer.BatchMLAPagedAttentionWrapper.run` (flashinfer_mla_backend.py:472-541) runs with page size 1.  This module validates, fills the C struct and launches; nothing in it computes, copies or synchronises, and the only
+`flashinfer.BatchMLAPagedAttentionWrapper.run` (flashinfer_mla_backend.py:472-541) runs with page size 1 — and P3: paged GQA attention
+(head dim 128, csrc/gqa_paged_bf16.hip), what `flashinfer.BatchDecodeWithPagedKVCacheWrapper` / `BatchPrefillWithPagedKVCacheWrapper` /
+the 128/128 ragged wrapper run for the GQA models (srt/layers/attention/flashinfer_backend.py); its decode form allocates the workspace
+of its KV split with torch.empty.  This module validates, fills the C struct and launches; nothing in it computes, copies or synchronises, and the only
 allocations are the outputs.  Anything the kernel does not serve raises RuntimeError — there is no library fallback.
 
 The log-sum-exp all three functions speak is BASE 2: lse = log2 sum_j 2^(sm_scale * log2(e) * q.k_j) (flashinfer's convention)."""
@@ -12,7 +15,7 @@ import ctypes
 
 import torch
 
-from ._lib import check, lib, stream_ptr
+from ._lib import check, cu_count, lib, stream_ptr
 
 _vp, _i64, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
 
@@ -193,4 +196,123 @@ def mla_prefill_paged(q_nope, q_pe, ckv, kpe, qo_indptr, kv_indptr, kv_indices, 
     a.qo_indptr, a.kv_indptr, a.kv_indices = qo_indptr.data_ptr(), kv_indptr.data_ptr(), kv_indices.data_ptr()
     a.kv_len_arr, a.out, a.lse = kv_len_arr.data_ptr(), out.data_ptr(), (lse.data_ptr() if lse is not None else None)
     check(lib.fl_mla_prefill_paged_bf16(ctypes.byref(a), stream_ptr(dev)), "fl_mla_prefill_paged_bf16")
+    return (out, lse) if return_lse else out
+
+
+class FlGqaPagedArgs(ctypes.Structure):
+    """Mirror of `struct FlGqaPagedArgs` in include/fluent_mi355.h (field order is ABI)."""
+
+    _fields_ = [
+        ("struct_bytes", _i32), ("batch", _i32), ("num_q_tokens", _i64), ("num_kv_slots", _i64), ("num_kv_indices", _i64),
+        ("num_qo_heads", _i32), ("num_kv_heads", _i32), ("head_dim", _i32), ("causal", _i32), ("sm_scale", ctypes.c_float),
+        ("decode_form", _i32), ("num_splits", _i32), ("reserved", _i32),
+        ("q", _vp), ("q_stride_token", _i64), ("q_stride_head", _i64),
+        ("k", _vp), ("k_stride_slot", _i64), ("k_stride_head", _i64),
+        ("v", _vp), ("v_stride_slot", _i64), ("v_stride_head", _i64),
+        ("qo_indptr", _vp), ("kv_indptr", _vp), ("kv_indices", _vp), ("out", _vp), ("lse", _vp),
+        ("workspace", _vp), ("workspace_bytes", _i64),
+    ]
+
+
+lib.fl_gqa_paged_attention_bf16.argtypes = [ctypes.POINTER(FlGqaPagedArgs), _vp]
+lib.fl_gqa_paged_attention_bf16.restype = ctypes.c_int
+
+GQA_HEAD_DIM, GQA_MAX_GROUP, GQA_DECODE_ROWS, GQA_MAX_SPLITS = 128, 16, 16, 16
+
+
+def gqa_num_splits(batch: int, num_kv_heads: int, cus: int) -> int:
+    """Slices the decode form cuts every request's KV into.  From SHAPES only (a captured graph stays valid when lengths change): enough
+    workgroups for two per CU, at most 16.  The rule is a GUESS: no other S was ever timed beside it.  The first measurement
+    (profiles/gqa_paged_first_measurement.txt; Hkv = 8, seq 4096, 256 CUs): B = 128 -> S = 1, 0.72 of 8 TB/s; B = 16 -> S = 4, 0.67;
+    B = 1 -> the cap of 16 (the rule asks for 64) leaves half the CUs idle, 15.8 us = 0.13."""
+    return max(1, min(GQA_MAX_SPLITS, -(-2 * cus // max(1, batch * num_kv_heads))))
+
+
+def _gqa_rows(name, t, heads, dev):
+    if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
+        raise RuntimeError(f"gqa_paged_attention: {name} must be a CUDA/HIP tensor on {dev}")
+    if t.dtype != torch.bfloat16:
+        raise RuntimeError(f"gqa_paged_attention: {name} is {t.dtype}; only bfloat16 is served")
+    if t.dim() != 3 or t.shape[2] != GQA_HEAD_DIM or (heads is not None and t.shape[1] != heads):
+        raise RuntimeError(f"gqa_paged_attention: {name} must be [rows, {heads or 'heads'}, {GQA_HEAD_DIM}] (other head dims, page sizes "
+                           f"other than 1 and the HND layout are not served), got {tuple(t.shape)}")
+    if t.numel() and (t.stride(2) != 1 or t.stride(0) % 8 or t.stride(1) % 8 or t.data_ptr() % 16):
+        raise RuntimeError(f"gqa_paged_attention: {name} needs a contiguous last dimension and 16-byte aligned rows, strides {t.stride()}")
+
+
+def _gqa_i32(name, t, dev, n=None):
+    if (not torch.is_tensor(t) or t.device != dev or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()
+            or (n is not None and t.numel() < n)):
+        raise RuntimeError(f"gqa_paged_attention: {name} must be a contiguous int32 vector on {dev}"
+                           + (f" with at least {n} entries" if n is not None else ""))
+
+
+def gqa_paged_attention(q, k_pool, v_pool, qo_indptr, kv_indptr, kv_indices, causal: bool, sm_scale: float | None = None,
+                        out=None, lse=None, return_lse: bool = False, q_len_fixed: bool = False):
+    """q [T, Hq, 128], k_pool / v_pool [slots, Hkv, 128] bf16 (any 16-byte aligned slot / head strides; nothing is copied),
+    Hq % Hkv == 0 with a group of at most 16 heads.  qo_indptr int32 [B + 1] or None (= one query token per request: decode, T == B),
+    kv_indptr int32 [>= B + 1], kv_indices int32 (one slot = one token) or None (= identity: request b's keys are rows
+    kv_indptr[b] .. kv_indptr[b + 1] of the pools themselves — the ragged form).  Writes o [T, Hq, 128] bf16 into `out` (allocated when
+    None) and, with `return_lse` or `lse` given, the BASE-2 lse [T, Hq] f32.  `causal` is bottom-right aligned; a row that sees no key
+    gets o = 0, lse = -inf; rows of no request are left unwritten; slot indices are clamped into [0, slots).
+
+    Which kernel form runs is decided from shapes alone (no host synchronisation): the decode form — waves split the KV, the KV of a
+    request is cut into gqa_num_splits() slices and merged by a second kernel — when every request has one query token (qo_indptr None)
+    or, with `q_len_fixed`, T / B tokens with T / B * (Hq / Hkv) <= 16; the row form otherwise."""
+    if not torch.is_tensor(q) or q.dim() != 3:
+        raise RuntimeError("gqa_paged_attention: q must be a [tokens, heads, 128] tensor")
+    dev = q.device
+    T, Hq = q.shape[:2]
+    _gqa_rows("q", q, None, dev)
+    if not torch.is_tensor(k_pool) or k_pool.dim() != 3:
+        raise RuntimeError("gqa_paged_attention: k_pool must be a [slots, kv heads, 128] tensor")
+    Hkv = k_pool.shape[1]
+    _gqa_rows("k_pool", k_pool, None, dev)
+    _gqa_rows("v_pool", v_pool, Hkv, dev)
+    if v_pool.shape[0] != k_pool.shape[0]:
+        raise RuntimeError("gqa_paged_attention: k_pool and v_pool differ in slots")
+    if Hkv < 1 or Hq % Hkv or Hq // Hkv > GQA_MAX_GROUP:
+        raise RuntimeError(f"gqa_paged_attention: {Hq} query heads over {Hkv} KV heads; the group must be whole and at most {GQA_MAX_GROUP}")
+    G = Hq // Hkv
+    _gqa_i32("kv_indptr", kv_indptr, dev, 1)
+    if qo_indptr is None:
+        B = kv_indptr.numel() - 1
+        if T != B:
+            raise RuntimeError(f"gqa_paged_attention: without qo_indptr every request has one query token, got {T} tokens for {B} requests")
+    else:
+        _gqa_i32("qo_indptr", qo_indptr, dev, 1)
+        B = qo_indptr.numel() - 1
+        _gqa_i32("kv_indptr", kv_indptr, dev, B + 1)
+    if kv_indices is not None:
+        _gqa_i32("kv_indices", kv_indices, dev)
+    if out is None:
+        out = torch.empty(T, Hq, GQA_HEAD_DIM, dtype=torch.bfloat16, device=dev)
+    elif (not torch.is_tensor(out) or out.dtype != torch.bfloat16 or out.device != dev or tuple(out.shape) != (T, Hq, GQA_HEAD_DIM)
+          or not out.is_contiguous()):
+        raise RuntimeError(f"gqa_paged_attention: out must be a contiguous bf16 [{T}, {Hq}, {GQA_HEAD_DIM}] tensor on {dev}")
+    if lse is None:
+        lse = torch.empty(T, Hq, dtype=torch.float32, device=dev) if return_lse else None
+    elif (not torch.is_tensor(lse) or lse.dtype != torch.float32 or lse.device != dev or tuple(lse.shape) != (T, Hq)
+          or not lse.is_contiguous()):
+        raise RuntimeError(f"gqa_paged_attention: lse must be a contiguous f32 [{T}, {Hq}] tensor on {dev}")
+    decode = qo_indptr is None or (bool(q_len_fixed) and B > 0 and T % B == 0 and T // B * G <= GQA_DECODE_ROWS)
+    S = gqa_num_splits(B, Hkv, cu_count(dev)) if decode and B > 0 else 1
+    # the partial states of the splits: from the caching allocator (under capture: the graph's pool), not the caller's workspace buffer
+    ws = torch.empty(S * T * Hq * (GQA_HEAD_DIM + 1), dtype=torch.float32, device=dev) if S > 1 else None
+    a = FlGqaPagedArgs()
+    a.struct_bytes = ctypes.sizeof(FlGqaPagedArgs)
+    a.batch, a.num_q_tokens, a.num_kv_slots = B, T, k_pool.shape[0]
+    a.num_kv_indices = k_pool.shape[0] if kv_indices is None else kv_indices.numel()
+    a.num_qo_heads, a.num_kv_heads, a.head_dim, a.causal = Hq, Hkv, GQA_HEAD_DIM, int(bool(causal))
+    a.sm_scale = float(GQA_HEAD_DIM ** -0.5 if sm_scale is None else sm_scale)
+    a.decode_form, a.num_splits = int(decode), S
+    a.q, a.q_stride_token, a.q_stride_head = q.data_ptr(), q.stride(0), q.stride(1)
+    a.k, a.k_stride_slot, a.k_stride_head = k_pool.data_ptr(), k_pool.stride(0), k_pool.stride(1)
+    a.v, a.v_stride_slot, a.v_stride_head = v_pool.data_ptr(), v_pool.stride(0), v_pool.stride(1)
+    a.qo_indptr = qo_indptr.data_ptr() if qo_indptr is not None else None
+    a.kv_indptr = kv_indptr.data_ptr()
+    a.kv_indices = kv_indices.data_ptr() if kv_indices is not None else None
+    a.out, a.lse = out.data_ptr(), (lse.data_ptr() if lse is not None else None)
+    a.workspace, a.workspace_bytes = (ws.data_ptr(), ws.numel() * 4) if ws is not None else (None, 0)
+    check(lib.fl_gqa_paged_attention_bf16(ctypes.byref(a), stream_ptr(dev)), "fl_gqa_paged_attention_bf16")
     return (out, lse) if return_lse else out
