@@ -47,7 +47,8 @@ typedef void* fl_stream_t;
  *      fl_mla_prefill_paged_bf16 with its own FlMlaPrefillArgs, struct_bytes first, checked;
  *      fl_sampling_softmax / fl_sampling_renorm / fl_sampling_sample with FlSamplingArgs, struct_bytes first, checked;
  *      fl_spec_verify_greedy / fl_spec_verify_sample with FlSpecVerifyArgs, struct_bytes first, checked;
- *      fl_gqa_paged_attention_bf16 with FlGqaPagedArgs, struct_bytes first, checked.) */
+ *      fl_gqa_paged_attention_bf16 with FlGqaPagedArgs, struct_bytes first, checked;
+ *      fl_gqa_paged_attention_fp8kv over the UNCHANGED FlGqaPagedArgs, the two scales as plain arguments.) */
 #define FL_ABI_VERSION 102
 const char* fl_last_error(void);
 int fl_version(void);
@@ -708,6 +709,13 @@ typedef struct FlGqaPagedArgs {
   int64_t workspace_bytes;
 } FlGqaPagedArgs;
 int fl_gqa_paged_attention_bf16(const FlGqaPagedArgs* args, fl_stream_t stream);
+/* The same statement over an fp8 KV cache (csrc/gqa_paged_fp8kv.hip): `k` / `v` are OCP e4m3fn BYTES [N, Hkv, 128], their strides are in
+ * elements = bytes and must be multiples of 16 with 16-byte aligned base pointers; q / out stay bf16.
+ *   o = v_scale softmax(sm_scale k_scale q k8^T + mask) v8,   lse = log2 sum_j 2^(sm_scale k_scale log2e q . k8)   (base 2)
+ * The bytes are dequantised exactly into the bf16 MFMAs of the bf16 kernel (fp32 accumulation, bf16 P; neither q nor P is quantised);
+ * k_scale enters the logit scale, v_scale the final normaliser in fp32 (split partials carry it).  Both scales are finite and positive
+ * (1.0f = none); a NaN byte of a visible token propagates.  Every other field, limit and guarantee is fl_gqa_paged_attention_bf16's. */
+int fl_gqa_paged_attention_fp8kv(const FlGqaPagedArgs* args, float k_scale, float v_scale, fl_stream_t stream);
 
 #ifdef __cplusplus
 }

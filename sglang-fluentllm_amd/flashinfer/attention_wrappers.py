@@ -101,6 +101,8 @@ class BatchPrefillWithRaggedKVCacheWrapper(_InertWrapper):
             for name, t, heads in (("q", q, pl["num_qo_heads"]), ("k", k, pl["num_kv_heads"]), ("v", v, pl["num_kv_heads"])):
                 if not torch.is_tensor(t) or t.dim() != 3 or t.shape[1] != heads:
                     raise RuntimeError(f"{what}: {name} must be a [tokens, {heads}, 128] tensor as planned")
+                if t.dtype != torch.bfloat16:   # (the binding would take fp8 k / v for a cache; fresh activations are bf16)
+                    raise RuntimeError(f"{what}: {name} is {t.dtype}; only bfloat16 is served")
             return prefill.gqa_paged_attention(q, k, v, pl["qo_indptr"], pl["kv_indptr"], None, bool(causal), sm_scale,
                                                return_lse=return_lse)
         if pl["num_kv_heads"] != pl["num_qo_heads"]:
@@ -207,10 +209,14 @@ class _PagedGqaWrapper:
     """What BatchDecodeWithPagedKVCacheWrapper and BatchPrefillWithPagedKVCacheWrapper share: `plan` RECORDS and never raises (built with
     `use_cuda_graph` it also copies the index arrays into the constructor's buffers — device-side, non-blocking, skipped where the argument
     already is the buffer — which `run` then reads: a captured launch sees the next plan's values); `run` checks everything and launches
-    csrc/gqa_paged_bf16.hip through fluent_mi355.prefill.gqa_paged_attention.  Served: bf16 q and KV, head dims 128 / 128, page size 1, NHD,
-    num_qo_heads a multiple of num_kv_heads with a group of at most 16, causal (bottom-right aligned) or not; `sm_scale=None` = 128 ** -0.5.
-    Refused at `run` with RuntimeError: logits_soft_cap > 0, window_left != -1, k_scale / v_scale other than None or 1.0, custom masks,
-    positional encodings, other data types, head dims, page sizes or layouts, a single-tensor KV cache, any other option."""
+    csrc/gqa_paged_bf16.hip or, for a plan with `kv_data_type` / `data_type` float8_e4m3fn, csrc/gqa_paged_fp8kv.hip through
+    fluent_mi355.prefill.gqa_paged_attention.  Served: bf16 q; a bf16 or float8_e4m3fn KV cache (the pools must have the planned type), the
+    fp8 one with `k_scale` / `v_scale` = None (1.0) or finite positive Python numbers: o = v_scale softmax(sm_scale k_scale q K^T) V, the
+    lse carries k_scale; head dims 128 / 128, page size 1, NHD, num_qo_heads a multiple of num_kv_heads with a group of at most 16, causal
+    (bottom-right aligned) or not; `sm_scale=None` = 128 ** -0.5.
+    Refused at `run` with RuntimeError: logits_soft_cap > 0, window_left != -1, k_scale / v_scale other than None or 1.0 on a bf16 cache,
+    a zero, negative, non-finite or tensor scale, float8_e5m2 / uint8 or any other KV type, fp8 q, pools that are not of the planned type,
+    custom masks, positional encodings, other head dims, page sizes or layouts, a single-tensor KV cache, any other option."""
     _what = "paged GQA wrapper"
 
     def _init(self, float_workspace_buffer, kv_layout, use_cuda_graph, bufs):
@@ -248,6 +254,8 @@ class _PagedGqaWrapper:
         self._plan = self.last_plan = None
 
     def _launch(self, q, paged_kv_cache, run_opts, return_lse, out=None, lse=None):
+        import math
+
         from fluent_mi355 import prefill
         import torch
 
@@ -263,16 +271,26 @@ class _PagedGqaWrapper:
             raise RuntimeError(f"{what}: logits_soft_cap is not served by the MI355X GQA kernel")
         if opts.pop("window_left", -1) != -1:
             raise RuntimeError(f"{what}: sliding windows (window_left != -1) are not served")
+        q_dt, kv_dt = opts.pop("q_data_type", None), opts.pop("kv_data_type", None)
+        if q_dt is not None and q_dt not in (torch.bfloat16, "bfloat16"):
+            raise RuntimeError(f"{what}: q_data_type={q_dt}; only bfloat16 is served")
+        fp8 = kv_dt in (torch.float8_e4m3fn, "float8_e4m3fn")
+        if kv_dt is not None and not fp8 and kv_dt not in (torch.bfloat16, "bfloat16"):
+            raise RuntimeError(f"{what}: kv_data_type={kv_dt}; only bfloat16 and float8_e4m3fn are served")
+        scales = {}
         for name in ("k_scale", "v_scale"):
-            s = opts.pop(name, None)
-            if s is not None and float(s) != 1.0:
-                raise RuntimeError(f"{what}: {name}={s!r}; an fp8 / scaled KV cache is not served")
+            s = scales[name] = opts.pop(name, None)
+            if s is None:
+                continue
+            if not fp8:
+                if float(s) != 1.0:
+                    raise RuntimeError(f"{what}: {name}={s!r}; an fp8 / scaled KV cache is not served with a bfloat16 plan")
+                scales[name] = None
+            elif isinstance(s, bool) or not isinstance(s, (int, float)) or not math.isfinite(s) or s <= 0:
+                raise RuntimeError(f"{what}: {name}={s!r}; a scale is None or a finite positive Python number (a tensor would have to be "
+                                   "read on the host, which a captured launch cannot do)")
         if opts.pop("pos_encoding_mode", "NONE") != "NONE":
             raise RuntimeError(f"{what}: positional encodings inside attention are not served")
-        for name in ("q_data_type", "kv_data_type"):
-            dt = opts.pop(name, None)
-            if dt is not None and dt not in (torch.bfloat16, "bfloat16"):
-                raise RuntimeError(f"{what}: {name}={dt}; only bfloat16 is served")
         opts.pop("non_blocking", None)
         opts.pop("enable_pdl", None)
         q_len_fixed = bool(opts.pop("q_len_fixed", False))
@@ -293,8 +311,11 @@ class _PagedGqaWrapper:
         if (not torch.is_tensor(q) or q.dim() != 3 or q.shape[1] != pl["num_qo_heads"] or not torch.is_tensor(k_pool) or k_pool.dim() != 3
                 or k_pool.shape[1] != pl["num_kv_heads"]):
             raise RuntimeError(f"{what}: q must be [tokens, {pl['num_qo_heads']}, 128] and the pools [slots, {pl['num_kv_heads']}, 128] as planned")
+        want = torch.float8_e4m3fn if fp8 else torch.bfloat16
+        if k_pool.dtype != want or not torch.is_tensor(v_pool) or v_pool.dtype != want:
+            raise RuntimeError(f"{what}: the plan says a {want} KV cache, the pools are {k_pool.dtype} / {getattr(v_pool, 'dtype', None)}")
         return prefill.gqa_paged_attention(q, k_pool, v_pool, pl.get("qo_indptr"), pl["kv_indptr"], pl["kv_indices"], causal, sm_scale,
-                                           out=out, lse=lse, return_lse=return_lse, q_len_fixed=q_len_fixed)
+                                           out=out, lse=lse, return_lse=return_lse, q_len_fixed=q_len_fixed, **scales)
 
 
 class BatchDecodeWithPagedKVCacheWrapper(_PagedGqaWrapper):

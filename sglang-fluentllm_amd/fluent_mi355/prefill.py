@@ -3,7 +3,7 @@
 layers/attention/chunker.py:304) and `flashinfer.merge_state` (models/deepseek_v2.py:1037-1071) run on the DeepSeek-V3 / LongCat MLA
 prompt path — and absorbed paged MLA attention over token-indexed KV (csrc/mla_prefill_bf16.hip), what
 `flashinfer.BatchMLAPagedAttentionWrapper.run` (flashinfer_mla_backend.py:472-541) runs with page size 1 — and P3: paged GQA attention
-(head dim 128, csrc/gqa_paged_bf16.hip), what `flashinfer.BatchDecodeWithPagedKVCacheWrapper` / `BatchPrefillWithPagedKVCacheWrapper` /
+(head dim 128, csrc/gqa_paged_bf16.hip, and over an fp8 e4m3 KV cache csrc/gqa_paged_fp8kv.hip), what `flashinfer.BatchDecodeWithPagedKVCacheWrapper` / `BatchPrefillWithPagedKVCacheWrapper` /
 the 128/128 ragged wrapper run for the GQA models (srt/layers/attention/flashinfer_backend.py); its decode form allocates the workspace
 of its KV split with torch.empty.  This module validates, fills the C struct and launches; nothing in it computes, copies or synchronises, and the only
 allocations are the outputs.  Anything the kernel does not serve raises RuntimeError — there is no library fallback.
@@ -12,6 +12,7 @@ The log-sum-exp all three functions speak is BASE 2: lse = log2 sum_j 2^(sm_scal
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 
@@ -216,6 +217,8 @@ class FlGqaPagedArgs(ctypes.Structure):
 
 lib.fl_gqa_paged_attention_bf16.argtypes = [ctypes.POINTER(FlGqaPagedArgs), _vp]
 lib.fl_gqa_paged_attention_bf16.restype = ctypes.c_int
+lib.fl_gqa_paged_attention_fp8kv.argtypes = [ctypes.POINTER(FlGqaPagedArgs), ctypes.c_float, ctypes.c_float, _vp]
+lib.fl_gqa_paged_attention_fp8kv.restype = ctypes.c_int
 
 GQA_HEAD_DIM, GQA_MAX_GROUP, GQA_DECODE_ROWS, GQA_MAX_SPLITS = 128, 16, 16, 16
 
@@ -228,15 +231,18 @@ def gqa_num_splits(batch: int, num_kv_heads: int, cus: int) -> int:
     return max(1, min(GQA_MAX_SPLITS, -(-2 * cus // max(1, batch * num_kv_heads))))
 
 
-def _gqa_rows(name, t, heads, dev):
+def _gqa_rows(name, t, heads, dev, dtype=torch.bfloat16):
     if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
         raise RuntimeError(f"gqa_paged_attention: {name} must be a CUDA/HIP tensor on {dev}")
-    if t.dtype != torch.bfloat16:
-        raise RuntimeError(f"gqa_paged_attention: {name} is {t.dtype}; only bfloat16 is served")
+    if t.dtype != dtype:
+        raise RuntimeError(f"gqa_paged_attention: {name} is {t.dtype}; " + (
+            f"the other pool is {dtype}" if dtype != torch.bfloat16 else "only bfloat16 is served" if name == "q" else
+            "only bfloat16 and float8_e4m3fn pools (both alike) are served"))
     if t.dim() != 3 or t.shape[2] != GQA_HEAD_DIM or (heads is not None and t.shape[1] != heads):
         raise RuntimeError(f"gqa_paged_attention: {name} must be [rows, {heads or 'heads'}, {GQA_HEAD_DIM}] (other head dims, page sizes "
                            f"other than 1 and the HND layout are not served), got {tuple(t.shape)}")
-    if t.numel() and (t.stride(2) != 1 or t.stride(0) % 8 or t.stride(1) % 8 or t.data_ptr() % 16):
+    per16 = 16 // t.element_size()   # elements in 16 bytes: 8 (bf16) or 16 (fp8)
+    if t.numel() and (t.stride(2) != 1 or t.stride(0) % per16 or t.stride(1) % per16 or t.data_ptr() % 16):
         raise RuntimeError(f"gqa_paged_attention: {name} needs a contiguous last dimension and 16-byte aligned rows, strides {t.stride()}")
 
 
@@ -248,8 +254,9 @@ def _gqa_i32(name, t, dev, n=None):
 
 
 def gqa_paged_attention(q, k_pool, v_pool, qo_indptr, kv_indptr, kv_indices, causal: bool, sm_scale: float | None = None,
-                        out=None, lse=None, return_lse: bool = False, q_len_fixed: bool = False):
-    """q [T, Hq, 128], k_pool / v_pool [slots, Hkv, 128] bf16 (any 16-byte aligned slot / head strides; nothing is copied),
+                        out=None, lse=None, return_lse: bool = False, q_len_fixed: bool = False, k_scale=None, v_scale=None):
+    """q [T, Hq, 128] bf16, k_pool / v_pool [slots, Hkv, 128] both bf16 or both float8_e4m3fn — the pools' dtype picks the kernel,
+    csrc/gqa_paged_bf16.hip or csrc/gqa_paged_fp8kv.hip (any 16-byte aligned slot / head strides; nothing is copied),
     Hq % Hkv == 0 with a group of at most 16 heads.  qo_indptr int32 [B + 1] or None (= one query token per request: decode, T == B),
     kv_indptr int32 [>= B + 1], kv_indices int32 (one slot = one token) or None (= identity: request b's keys are rows
     kv_indptr[b] .. kv_indptr[b + 1] of the pools themselves — the ragged form).  Writes o [T, Hq, 128] bf16 into `out` (allocated when
@@ -258,7 +265,11 @@ def gqa_paged_attention(q, k_pool, v_pool, qo_indptr, kv_indptr, kv_indices, cau
 
     Which kernel form runs is decided from shapes alone (no host synchronisation): the decode form — waves split the KV, the KV of a
     request is cut into gqa_num_splits() slices and merged by a second kernel — when every request has one query token (qo_indptr None)
-    or, with `q_len_fixed`, T / B tokens with T / B * (Hq / Hkv) <= 16; the row form otherwise."""
+    or, with `q_len_fixed`, T / B tokens with T / B * (Hq / Hkv) <= 16; the row form otherwise.
+
+    fp8 pools: o = v_scale softmax(sm_scale k_scale q K8^T + mask) V8, and the lse carries k_scale; the bytes are dequantised exactly, q and
+    P stay bf16.  `k_scale` / `v_scale` are None (= 1.0) or finite positive Python numbers; a tensor is refused (reading it would
+    synchronise the host and break a capture).  bf16 pools take no scale other than None / 1.0."""
     if not torch.is_tensor(q) or q.dim() != 3:
         raise RuntimeError("gqa_paged_attention: q must be a [tokens, heads, 128] tensor")
     dev = q.device
@@ -267,8 +278,17 @@ def gqa_paged_attention(q, k_pool, v_pool, qo_indptr, kv_indptr, kv_indices, cau
     if not torch.is_tensor(k_pool) or k_pool.dim() != 3:
         raise RuntimeError("gqa_paged_attention: k_pool must be a [slots, kv heads, 128] tensor")
     Hkv = k_pool.shape[1]
-    _gqa_rows("k_pool", k_pool, None, dev)
-    _gqa_rows("v_pool", v_pool, Hkv, dev)
+    fp8 = k_pool.dtype == torch.float8_e4m3fn
+    _gqa_rows("k_pool", k_pool, None, dev, k_pool.dtype if fp8 else torch.bfloat16)
+    _gqa_rows("v_pool", v_pool, Hkv, dev, k_pool.dtype)
+    scales = []
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s is not None and (isinstance(s, bool) or not isinstance(s, (int, float)) or not math.isfinite(s) or s <= 0):
+            raise RuntimeError(f"gqa_paged_attention: {name}={s!r}; a scale is None or a finite positive Python number (a tensor would "
+                               "have to be read on the host)")
+        if s is not None and not fp8 and float(s) != 1.0:
+            raise RuntimeError(f"gqa_paged_attention: {name}={s!r} with bf16 pools; only an fp8 KV cache is scaled")
+        scales.append(1.0 if s is None else float(s))
     if v_pool.shape[0] != k_pool.shape[0]:
         raise RuntimeError("gqa_paged_attention: k_pool and v_pool differ in slots")
     if Hkv < 1 or Hq % Hkv or Hq // Hkv > GQA_MAX_GROUP:
@@ -314,5 +334,8 @@ def gqa_paged_attention(q, k_pool, v_pool, qo_indptr, kv_indptr, kv_indices, cau
     a.kv_indices = kv_indices.data_ptr() if kv_indices is not None else None
     a.out, a.lse = out.data_ptr(), (lse.data_ptr() if lse is not None else None)
     a.workspace, a.workspace_bytes = (ws.data_ptr(), ws.numel() * 4) if ws is not None else (None, 0)
-    check(lib.fl_gqa_paged_attention_bf16(ctypes.byref(a), stream_ptr(dev)), "fl_gqa_paged_attention_bf16")
+    if fp8:
+        check(lib.fl_gqa_paged_attention_fp8kv(ctypes.byref(a), scales[0], scales[1], stream_ptr(dev)), "fl_gqa_paged_attention_fp8kv")
+    else:
+        check(lib.fl_gqa_paged_attention_bf16(ctypes.byref(a), stream_ptr(dev)), "fl_gqa_paged_attention_bf16")
     return (out, lse) if return_lse else out
